@@ -34,6 +34,9 @@ T_START = time.time()
 HBM_PEAK_GBS = 8000.0                      # MI355X_MICROARCH.md: 8.0 TB/s spec
 PCIE_SPEC_GBS = 63.0                       # PCIe Gen5 x16 per direction
 SEARCH_BYTES_PER_BASE = 160                # one 64-byte block + 8 + 8 bytes on each side
+DUMP_BUDGET_BYTES = 64 << 20               # --dump-outputs: all files together
+DUMP_WINDOW = 2048                         # bytes of the stream per sampled window
+DUMP_SEED = 20240917                       # the windows and blocks a sampled dump takes depend on this and on the result's size only
 
 
 def log(msg):
@@ -89,7 +92,12 @@ def main():
     ap.add_argument("--keep-pool", action="store_true",
                     help="do not return the library's pooled memory to the driver after the inputs are built (under rocprofv3 --pmc memory released "
                          "with hipMemRelease does not come back: at 2 x 50 Gbase the merge then finds 118 GB less than it should)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (float32 stream bytes, float64 counts; a fixed, seeded "
+                         "sample when the result is larger than %d MB), for comparing the outputs of two builds" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the result of the last timed step is verified)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself (it has not touched the GPU) and
@@ -415,6 +423,7 @@ def measure(env, args):
     barrier()
     elapsed = time.perf_counter() - t0
     prof = pkg.profile_read()
+    dumped = dump_outputs(np, last, args.dump_outputs, rank, world) if args.dump_outputs else None
     shard_phases = None
     if sharded and shard_times.get("merges"):
         # rank 0's view, per merge of the timed region; the maximum over ranks of the whole step is `ms_per_step`
@@ -625,7 +634,7 @@ def measure(env, args):
         "sharded_phases_rank0": shard_phases, "partitioned_phases_rank0": part_phases,
         "roofline": roofline, "job_roofline": job, "kernel_ms_per_step": kernel_ms,
         "host_to_host": host, "peak_device_bytes": peak_device,
-        "cpu_baseline": cpu, "verified": verified, "verification": checks,
+        "cpu_baseline": cpu, "verified": verified, "verification": checks, "dump_outputs": dumped,
     }
 
 
@@ -721,6 +730,73 @@ def launch_ranks(world, same_device=False):
         log("a rank exited with code %d" % rc)
     return rc if rc >= 0 else 1
 
+
+def dump_outputs(np, res, path, rank, world):
+    """--dump-outputs: what the caller of the timed path holds after the last timed step, as .npy files under `path` -- the native byte
+    stream (float32, one element per byte), the header counts and, for a whole index, C and the block samples (float64: every count stays
+    below 2^53).  A stream larger than the budget is dumped as windows at seeded offsets (the first and the last window always among them),
+    samples of more blocks than the budget holds at seeded blocks; the offsets and block numbers are dumped next to them.  The ranks of a
+    sharded run (N > 1) dump their own slice of the result, with _rank<r> in the file names."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    sliced = hasattr(res, "byte_first")                            # a Slice of a sharded result; otherwise the whole merged Index
+    nbytes = res.nbytes
+    out, notes = {}, {}
+    stream_cap = DUMP_BUDGET_BYTES // 2 // 4                       # half of the budget for the stream, 4 bytes per element
+    if sliced:
+        raw = res.data()                                           # this rank's byte range of the stream
+
+        def read(first, count):
+            return raw[first: first + count]
+    else:
+        ptr, _ = res.device_data()
+        hip = ctypes.CDLL("libamdhip64.so.7")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+
+        def read(first, count):
+            buf = np.zeros(count, dtype=np.uint8)
+            if count and hip.hipMemcpy(buf.ctypes.data, ptr + first, count, 2) != 0:
+                raise RuntimeError("--dump-outputs: hipMemcpy of the result's bytes failed")
+            return buf
+    if nbytes <= stream_cap:
+        out["stream"] = read(0, nbytes).astype(np.float32)
+        out["stream_offsets"] = np.zeros(1, dtype=np.float64)
+    else:
+        n = stream_cap // DUMP_WINDOW
+        starts = np.unique(np.concatenate([[0, nbytes - DUMP_WINDOW], rng.integers(0, nbytes - DUMP_WINDOW + 1, n - 2)]))
+        out["stream"] = np.stack([read(int(s), DUMP_WINDOW) for s in starts]).astype(np.float32)
+        out["stream_offsets"] = starts.astype(np.float64)
+        notes["stream"] = "%d windows of %d bytes" % (starts.size, DUMP_WINDOW)
+    header = [res.total_nbytes, nbytes, res.byte_first if sliced else 0]
+    if not sliced:
+        header = [res.bases, res.sequences] + header
+        out["C"] = res.C.astype(np.float64)
+        blocks = res.blocks
+        block_cap = DUMP_BUDGET_BYTES // 4 // (8 * 8)              # a quarter of the budget for the samples (block number, end, 6 counts)
+        if blocks * 56 <= 8 << 30:                                 # the library hands out the samples whole: at most 8 GB of host memory for them
+            be, cum = res.samples()
+            if blocks <= block_cap:
+                pick = np.arange(blocks)
+            else:
+                pick = np.unique(np.concatenate([[0, blocks - 1], rng.integers(0, blocks, block_cap - 2)]))
+                notes["samples"] = "%d of %d blocks" % (pick.size, blocks)
+            out["sample_blocks"] = pick.astype(np.float64)
+            out["sample_block_ends"] = be[pick].astype(np.float64)
+            out["sample_counts"] = cum[:, pick].astype(np.float64)
+            del be, cum
+        else:
+            notes["samples"] = "not dumped: %d blocks" % blocks
+    out["header"] = np.array(header, dtype=np.float64)
+    suffix = ("_rank%d" % rank) if world > 1 else ""
+    files = {}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), arr)
+        files[name + suffix] = list(arr.shape)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BUDGET_BYTES, total
+    if rank == 0:
+        log("outputs of the last timed step: %d files, %.1f MB in %s %s" % (len(files), total / 1e6, path, notes or ""))
+    return {"dir": os.path.abspath(path), "files": files, "bytes": int(total), "sampled": notes or None}
 
 def verify_full_size(pkg, synth, np, last, meta, args, wargs, load_inputs):
     """Size-independent checks of the full-size result: C additivity and header, `verify_reads` reads extracted from the merged

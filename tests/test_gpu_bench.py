@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,6 +53,26 @@ def test_bench_single_gpu_small(bwtm):
     assert d["verification"]["frontier_equals_walk"] is True and d["verification"]["extracted_reads_count"] >= 10000
     h = d["host_to_host"]
     assert h["value"] > 0 and h["pcie"]["h2d_GBs"] > 1 and h["bytes"]["d2h_data"] == d["config"]["native_bytes"][2]
+
+
+def test_bench_dump_outputs_are_reproducible(bwtm, tmp_path):
+    """--dump-outputs: the last timed step's result as float .npy files within 64 MB; the same arguments with another number of timed steps
+    dump the same arrays, and they agree with the sizes and counts of the line."""
+    lines, dumps = [], []
+    for steps in (1, 3):
+        d = str(tmp_path / ("s%d" % steps))
+        lines.append(run_bench([sys.executable, "bench.py", "--reads", "200000", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+                                "--no-host", "--target", "off", "--dump-outputs", d]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    for line in lines:
+        assert line["verified"] is True and line["ms_per_step"] > 0 and line["dump_outputs"]["bytes"] <= 64 << 20
+    assert lines[0]["steps"] == 1 and lines[1]["steps"] == 3
+    a, b = dumps
+    assert set(a) == set(b) == {"stream", "stream_offsets", "C", "header", "sample_blocks", "sample_block_ends", "sample_counts"}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and all(np.array_equal(a[k], b[k]) for k in a)
+    cfg = lines[0]["config"]
+    assert a["header"].tolist() == [sum(cfg["bases"]), 2 * 200000, cfg["native_bytes"][2], cfg["native_bytes"][2], 0]
+    assert a["C"][-1] == sum(cfg["bases"]) and a["stream"].max() <= 255 and a["stream"].any()
 
 
 def test_bench_target_record_and_traffic_check(bwtm):
