@@ -29,7 +29,9 @@ namespace
 // device memory read in place when on_device), first_position = the position block b0 begins at, counts_before[c] = occurrences of c before it.
 int index_upload_window(const u8* data, u64 nbytes, u64 first_position, const u64 counts_before[6], u64 bases, u64 sequences, const u64 C[7], bool on_device, bwtm_index** out)
 {
-  if(!out || !data || nbytes == 0 || !counts_before || !C) { return fail(BWTM_EINVAL, "bwtm_index_upload_window: null argument"); }
+  if(!out || (nbytes > 0 && !data) || !counts_before || !C) { return fail(BWTM_EINVAL, "bwtm_index_upload_window: null argument"); }
+  // an empty index (0 bases) is the one whose share holds no bytes: its window is the single empty record, as bwtm_index_upload makes it
+  if(nbytes == 0 && bases != 0) { return fail(BWTM_EINVAL, "bwtm_index_upload_window: no bytes of an index of %llu positions", (unsigned long long)bases); }
   u64 before = 0; for(int c = 0; c < 6; c++) { before += counts_before[c]; }
   if(before != first_position || first_position > bases) { return fail(BWTM_EINVAL, "bwtm_index_upload_window: the counts before the bytes add up to %llu, their first position is %llu", (unsigned long long)before, (unsigned long long)first_position); }
   if(on_device && ((uintptr_t)data & 15) != 0) { return fail(BWTM_EINVAL, "bwtm_index_upload_window: a device share must be 16-byte aligned (whole 64-byte blocks of a 16-byte aligned stream)"); }
@@ -37,10 +39,11 @@ int index_upload_window(const u8* data, u64 nbytes, u64 first_position, const u6
   x->ctx = t_ctx; x->nbytes = nbytes;
   auto body = [&]() -> int
   {
-    if(on_device) { x->borrowed = data; }
+    const bool borrow = on_device && nbytes > 0;                     // (an empty share gets the 16 zero bytes of padding of its own)
+    if(borrow) { x->borrowed = data; }
     else { TRY(alloc_native(x->data, nbytes)); }
     // the product's upload pipeline on the share: block lengths and group counts, their scans; the stream's verdict and totals come back
-    int rc = upload_queue(x, on_device ? nullptr : data);
+    int rc = upload_queue(x, (borrow || nbytes == 0) ? nullptr : data);
     if(rc == BWTM_OK) { rc = upload_scan(x, 0); }
     hipError_t e1 = hipStreamSynchronize(CTX.copy_stream), e2 = hipStreamSynchronize(CTX.stream);
     if(rc != BWTM_OK) { return rc; }
@@ -201,7 +204,7 @@ struct HostRank
 extern "C" int bwtm_partition_cuts_host(const bwtm_host_index* a, const bwtm_host_index* b, int parts, int kmer, uint64_t* cut_a, uint64_t* cut_b)
 {
   if(!a || !b || !cut_a || !cut_b || parts < 1 || parts > (int)PART_MAX) { return fail(BWTM_EINVAL, "bwtm_partition_cuts_host: bad argument"); }
-  if(!a->data || !a->cum || !b->data || !b->cum) { return fail(BWTM_EINVAL, "bwtm_partition_cuts_host: the inputs' bytes and cumulative sample arrays are needed"); }
+  if((!a->data && a->nbytes > 0) || !a->cum || (!b->data && b->nbytes > 0) || !b->cum) { return fail(BWTM_EINVAL, "bwtm_partition_cuts_host: the inputs' bytes and cumulative sample arrays are needed"); }
   if(kmer <= 0) { kmer = (parts <= 8 ? 4 : 5); }
   if(kmer > 8) { return fail(BWTM_EINVAL, "bwtm_partition_cuts_host: at most 8-mers"); }
   cut_a[0] = 0; cut_b[0] = 0; cut_a[parts] = a->bases; cut_b[parts] = b->bases;
@@ -241,7 +244,14 @@ extern "C" int bwtm_window_blocks(const bwtm_host_index* x, uint64_t pos_first, 
   if(!x || !x->cum || !block_first || !block_end || !first_position || !counts_before || pos_first > pos_last) { return fail(BWTM_EINVAL, "bwtm_window_blocks: bad argument"); }
   HostRank R{x};
   const u64 nb = x->blocks;
-  if(nb == 0) { return fail(BWTM_EINVAL, "bwtm_window_blocks: the index has no blocks"); }
+  if(nb == 0)
+  {
+    // an empty index: no bytes cover its (single, empty) record
+    if(x->bases != 0) { return fail(BWTM_EINVAL, "bwtm_window_blocks: an index of %llu positions without blocks", (unsigned long long)x->bases); }
+    *block_first = 0; *block_end = 0; *first_position = 0;
+    for(int c = 0; c < 6; c++) { counts_before[c] = 0; }
+    return BWTM_OK;
+  }
   const u64 first = pos_first & ~(u64)127, end = std::min<u64>(x->bases, (pos_last | 127) + 1);
   u64 l = 0, r = nb;                                                // last block that begins at or before `first`
   while(r - l > 1) { const u64 mid = (l + r) / 2; if(R.start(mid) <= first) { l = mid; } else { r = mid; } }

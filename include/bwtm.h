@@ -372,7 +372,8 @@ typedef struct { uint64_t bases, sequences; uint64_t C[BWTM_SIGMA + 1]; } bwtm_i
    cut_b: parts + 1 entries each (cut[0] = 0, cut[parts] = bases).  Pure host arithmetic; every part gets the same answer. */
 int bwtm_partition_cuts_host(const bwtm_host_index* a, const bwtm_host_index* b, int parts, int kmer, uint64_t* cut_a, uint64_t* cut_b);
 /* The 64-byte blocks [*block_first, *block_end) of x's stream whose records cover the positions [pos_first, pos_last], the position the first
-   of them begins at and the symbol counts before it (what bwtm_index_upload_window / bwtm_part_upload want).  Pure host arithmetic. */
+   of them begins at and the symbol counts before it (what bwtm_index_upload_window / bwtm_part_upload want); an index of 0 positions has no
+   blocks: [0, 0).  Pure host arithmetic. */
 int bwtm_window_blocks(const bwtm_host_index* x, uint64_t pos_first, uint64_t pos_last, uint64_t* block_first, uint64_t* block_end,
                        uint64_t* first_position, uint64_t counts_before[6]);
 
@@ -380,7 +381,7 @@ int bwtm_window_blocks(const bwtm_host_index* x, uint64_t pos_first, uint64_t po
    memory read in place when on_device != 0: 16-byte aligned, readable 16 bytes past the end), first_position = the position the first
    block begins at, counts_before[c] = occurrences of c before it, bases / sequences / C = the header of the WHOLE index.  The handle serves
    the records that lie wholly inside the bytes, addressed by their absolute numbers; only bwtm_ra_create_range, bwtm_interleave_range (with a
-   rank array finalized for a range the windows cover) and the bwtm_part_* calls take it. */
+   rank array finalized for a range the windows cover) and the bwtm_part_* calls take it.  An index of 0 positions is uploaded from 0 bytes. */
 int bwtm_index_upload_window(const uint8_t* data, uint64_t nbytes, uint64_t first_position, const uint64_t counts_before[6],
                              uint64_t bases, uint64_t sequences, const uint64_t C[BWTM_SIGMA + 1], int on_device, bwtm_index** out);
 uint64_t bwtm_index_record_bytes(const bwtm_index* index);        /* bytes of records the handle holds (a window: its share) */

@@ -20,22 +20,20 @@ def run_bench(cmd, timeout=900, env=None):
 
 
 def run_bench_shared_gpu(cmd, tries=3):
-    """Processes that SHARE one GPU are not a deployment (one process per GPU is), and on this ROCm release two processes that work one device
-    hard at the same time can corrupt each other's results whatever they run (tools/two_builders.py, profiles/r06_two_processes_one_gpu.txt: the
-    product search in all its forms, with and without the mapped-memory pool; never with one process).  bench.py takes turns where it can (input
-    builds, verification); the merges themselves must overlap.  A run that dies or does not verify is repeated (three runs in all) before it
-    counts as a failure of the path under test."""
+    """Processes that SHARE one GPU are not a deployment (one process per GPU is), and a run of several ranks on one card can be lost to the card
+    rather than to the path under test: a rank that crashes or a run that outlives its time limit (a rank that lost its peers gives up after
+    BWTM_GROUP_TIMEOUT) is repeated, three runs in all.  A run that COMPLETES must verify: a wrong answer fails at once and is never repeated
+    (the cross-process merge is compared with the oracle bit for bit in tests/test_gpu_parts_processes.py)."""
     last = None
     env = dict(os.environ, BWTM_GROUP_TIMEOUT="60")                    # a part that lost its peers gives up after a minute, not five
     for _ in range(tries):
         try:
             d = run_bench(cmd, timeout=240, env=env)                     # (a run takes ~15 s)
-        except (AssertionError, subprocess.TimeoutExpired) as e:
+        except (AssertionError, subprocess.TimeoutExpired) as e:         # a crash or a timeout: nothing was computed
             last = e
             continue
-        if d["verified"] is True:
-            return d
-        last = AssertionError("not verified: %r" % (d.get("verification"),))
+        assert d["verified"] is True, "completed but not verified (not repeated): %r" % (d.get("verification"),)
+        return d
     raise last
 
 

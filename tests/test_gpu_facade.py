@@ -149,6 +149,33 @@ def test_cli_one_thread_per_gpu(bwtm, oracle, tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("empty", ["first", "second"])
+def test_cli_partitioned_merge_with_an_empty_input(bwtm, oracle, tmp_path, empty):
+    """bwt_merge -g 0,0 (the merge over partitioned records, two parts) where one input holds 0 sequences and 0 bases: no fallback, and the
+    file equals the single-GPU one, whose BWT is the oracle's merge (the other input)."""
+    build_host()
+    e = oracle.FMI.from_text(np.zeros(0, dtype=np.uint8))
+    x = oracle.FMI.from_text(oracle.generate_reads(4300, 2000, 90))
+    a, b = (e, x) if empty == "first" else (x, e)
+    write_plain(tmp_path / "a.plain", a); write_plain(tmp_path / "b.plain", b)
+    assert os.path.getsize(tmp_path / ("a.plain" if empty == "first" else "b.plain")) == 0
+    m, _ = oracle.merge(a.clone(), b.clone(), threads=1)
+    exe = os.path.join(HOST, "bwt_merge")
+    outs = {}
+    for label, g in (("one", "0"), ("two", "0,0")):
+        out = subprocess.run([exe, "-g", g, "-i", "plain_default", str(tmp_path / "a.plain"), str(tmp_path / "b.plain"), str(tmp_path / (label + ".native"))],
+                             capture_output=True, text=True)
+        assert out.returncode == 0, out.stdout + out.stderr
+        if g != "0":
+            assert out.stderr.count("mergeMultiGPU(): 2 GPUs (partitioned records): upload ") == 1, out.stderr[-1500:]
+            assert "repeating it with sequence blocks" not in out.stderr
+        outs[label] = np.fromfile(tmp_path / (label + ".native"), dtype=np.uint8)
+    assert np.array_equal(outs["one"], outs["two"])
+    assert np.array_equal(m.data, x.data) and np.array_equal(outs["two"][32:32 + m.data.size], m.data)        # header (24 B) + byte count (8 B)
+    assert int(outs["two"][24:32].view(np.uint64)[0]) == m.data.size
+
+
+@pytest.mark.gpu
 def test_cli_two_distinct_gpus(bwtm, oracle, tmp_path):
     """bwt_merge -g 0,1: two host threads on two DEVICES, the rank-array shards combined by ncclAllReduce (the branch that
     contexts of one GPU never take).  Runs wherever two GPUs are visible; the file must equal the single-GPU one."""

@@ -6,6 +6,8 @@ stream, bit for bit; no part ever holds a whole index or the whole bitvector."""
 import numpy as np
 import pytest
 
+from parts_inputs import ODD_CASES, check_against_oracle, odd_collection, truly_empty, wide_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -36,13 +38,6 @@ def merge_parts(gpu, a, b, parts, kmer=0):
         return data, be, cum, out["stats"], out["cuts"]
     finally:
         out["release"]()
-
-
-def check_against_oracle(oracle, a, b, data, be, cum, threads=2):
-    m, _ = oracle.merge(a.clone(), b.clone(), threads=threads)
-    assert np.array_equal(data, m.data)
-    obe, ocum = m.samples
-    assert np.array_equal(be, obe) and np.array_equal(cum, ocum[:, :-1])
 
 
 @pytest.mark.parametrize("parts,kmer,range_ratio", [(1, 2, 8), (2, 1, 8), (3, 3, 0), (4, 4, 8), (8, 4, 8), (16, 3, 8), (2, 0, 0), (5, 4, 3), (4, 2, 1)])
@@ -91,10 +86,7 @@ def test_parts_with_mixed_read_lengths(gpu, oracle):
 @pytest.mark.parametrize("rr", [0, 4])
 def test_parts_wide_coordinates(gpu, oracle, rr):
     """Coordinates beyond 2^32: the high bytes travel through the cut search and the pulled tables."""
-    small_a = oracle.FMI.from_text(oracle.generate_reads(9301, 600, 60)); small_b = oracle.FMI.from_text(oracle.generate_reads(9302, 500, 70))
-    a = oracle.FMI.from_runs(small_a.symbols.astype(np.uint64), np.full(small_a.symbols.size, 120000, dtype=np.uint64))
-    assert a.bases > (1 << 32)
-    b = oracle.FMI.from_runs(small_b.symbols.astype(np.uint64), np.full(small_b.symbols.size, 2000, dtype=np.uint64))
+    a, b = wide_inputs(oracle)
     gpu.tune("frontier_epoch", 5); gpu.tune("range_ratio", rr)
     try:
         data, be, cum, stats, _ = merge_parts(gpu, a, b, 3, 2)
@@ -127,29 +119,10 @@ def test_parts_merge_of_repetitive_reads(gpu, oracle, glen, coverage):
     check_against_oracle(oracle, a, b, data, be, cum)
 
 
-@pytest.mark.parametrize("case", ["short", "one_base", "with_n", "tiny_b", "unequal", "empty_b"])
+@pytest.mark.parametrize("case", ODD_CASES)
 def test_parts_merge_of_odd_collections(gpu, oracle, case):
     """Collections on which most parts end up with nothing: windows of a single record, coinciding cuts, empty output ranges."""
-    rng = np.random.default_rng({"short": 1, "one_base": 2, "with_n": 3, "tiny_b": 4, "unequal": 5, "empty_b": 6}[case])
-
-    def reads(n, lo, hi, alphabet):
-        out = []
-        for _ in range(n):
-            out.append(rng.choice(alphabet, rng.integers(lo, hi + 1)).astype(np.uint8)); out.append(np.zeros(1, dtype=np.uint8))
-        return np.concatenate(out) if out else np.zeros(0, dtype=np.uint8)
-
-    if case == "short":
-        ta, tb = reads(400, 0, 3, [1, 2, 3, 4]), reads(300, 0, 4, [1, 2, 3, 4])
-    elif case == "one_base":
-        ta, tb = reads(200, 5, 40, [3]), reads(150, 1, 60, [3])
-    elif case == "with_n":
-        ta, tb = reads(300, 20, 50, [1, 2, 3, 4, 5, 5]), reads(250, 10, 70, [1, 2, 3, 4, 5])
-    elif case == "tiny_b":
-        ta, tb = reads(500, 30, 60, [1, 2, 3, 4]), reads(3, 5, 9, [1, 2, 3, 4])
-    elif case == "unequal":
-        ta, tb = reads(40, 10, 20, [1, 2, 3, 4]), reads(900, 40, 80, [1, 2, 3, 4])
-    else:
-        ta, tb = reads(300, 20, 50, [1, 2, 3, 4]), reads(1, 0, 0, [1])
+    ta, tb = odd_collection(case)
     a, b = oracle.FMI.from_text(ta), oracle.FMI.from_text(tb)
     for parts, kmer, rr in ((3, 2, 8), (5, 3, 0)):
         gpu.tune("range_ratio", rr)
@@ -158,6 +131,26 @@ def test_parts_merge_of_odd_collections(gpu, oracle, case):
         finally:
             gpu.tune("range_ratio", 8)
         check_against_oracle(oracle, a, b, data, be, cum, threads=1)
+
+
+@pytest.mark.parametrize("which", ["a", "b"])
+@pytest.mark.parametrize("parts", [2, 3])
+def test_parts_merge_with_a_truly_empty_input(gpu, oracle, which, parts):
+    """An input of 0 sequences and 0 bytes: every part's window of it is the single empty record, the cuts of that side are all 0, and (an
+    empty b) there is nothing to search.  The merge is the other input, as the oracle's is."""
+    a, b = truly_empty(oracle, which)
+    for kmer, rr in ((2, 8), (3, 0)):
+        gpu.tune("range_ratio", rr)
+        try:
+            data, be, cum, stats, cuts = merge_parts(gpu, a, b, parts, kmer)
+        finally:
+            gpu.tune("range_ratio", 8)
+        assert cuts[0 if which == "a" else 1] == [0] * (parts + 1)
+        m = check_against_oracle(oracle, a, b, data, be, cum, threads=1)
+        other = b if which == "a" else a
+        assert np.array_equal(m.data, other.data) and np.array_equal(data, other.data)
+        if which == "b":
+            assert all(s["elements"] == 0 and s["steps"] == 0 for s in stats)
 
 
 def test_a_group_serves_a_chain_of_merges(gpu, oracle):
