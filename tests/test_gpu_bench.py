@@ -38,7 +38,7 @@ def run_bench_shared_gpu(cmd, tries=3):
 
 
 def test_bench_single_gpu_small(bwtm):
-    d = run_bench([sys.executable, "bench.py", "--reads", "200000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--reads", "200000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000"])
     assert d["verified"] is True and d["n_gpus"] == 1 and d["value"] > 0
     # at this size bwtm_search picks the per-chain walk; config 2 runs the frontier search
     assert d["roofline"]["kernel"] in ("k_lf_walk_binned", "k_frontier_step") and d["roofline"]["bound"] == "hbm"
@@ -59,7 +59,7 @@ def test_bench_dump_outputs_are_reproducible(bwtm, tmp_path):
     lines, dumps = [], []
     for steps in (1, 3):
         d = str(tmp_path / ("s%d" % steps))
-        lines.append(run_bench([sys.executable, "bench.py", "--reads", "200000", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+        lines.append(run_bench([sys.executable, "bench.py", "--full", "--reads", "200000", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
                                 "--no-host", "--target", "off", "--dump-outputs", d]))
         dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
     for line in lines:
@@ -73,11 +73,27 @@ def test_bench_dump_outputs_are_reproducible(bwtm, tmp_path):
     assert a["C"][-1] == sum(cfg["bases"]) and a["stream"].max() <= 255 and a["stream"].any()
 
 
+def test_bench_plain_run_is_lean(bwtm, tmp_path):
+    """A run without --full sets up, warms up, times its steps, dumps its outputs and prints the line, nothing else: the line has the
+    headline and none of the records of --full, and it dumps the same arrays as a --full run of the same arguments, which verifies."""
+    args = ["--reads", "200000", "--steps", "2", "--warmup", "1"]
+    plain = run_bench([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / "plain")])
+    full = run_bench([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-host"] + args + ["--dump-outputs", str(tmp_path / "full")])
+    assert plain["full"] is False and full["full"] is True and full["verified"] is True and full["roofline"]["frac"] > 0
+    for key in ("verified", "roofline", "job_roofline", "kernel_ms_per_step", "host_to_host", "host_to_host_value", "cpu_baseline"):
+        assert plain[key] is None, key
+    assert "target" not in plain and plain["verification"] == {}
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "Gbases/s" and plain["higher_is_better"] is True and plain["dtype"] == "u64"
+    assert plain["metric"] == full["metric"] and plain["config"] == full["config"] and plain["steps"] == 2 and plain["warmup"] == 1
+    a, b = [{f[:-4]: np.load(os.path.join(str(tmp_path / d), f)) for f in os.listdir(str(tmp_path / d))} for d in ("plain", "full")]
+    assert set(a) == set(b) and "stream" in a and all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_bench_target_record_and_traffic_check(bwtm):
     """The `target` record of the default line (the north star's size in the driver's run), exercised at a small size: the second
     measurement runs after the first has released everything, carries its own verification, roofline and host-to-host leg and the ratio to
     the CPU baseline; and the stored PMC traffic is refused for a configuration it was not collected for, with the reason in the line."""
-    d = run_bench([sys.executable, "bench.py", "--reads", "3000000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000", "--no-config1",
+    d = run_bench([sys.executable, "bench.py", "--full", "--reads", "3000000", "--steps", "2", "--warmup", "1", "--cpu-sample-reads", "20000", "--no-config1",
                    "--target", "on", "--target-reads", "4500000", "--target-steps", "1"])
     t = d["target"]
     assert d["verified"] is True and t["verified"] is True and t["process"] == "child" and 0 < t["seconds"] <= d["process_seconds"]
@@ -114,7 +130,7 @@ def test_stored_traffic_entries_describe_this_code(bwtm):
 
 def test_bench_mixed_read_lengths(bwtm):
     """BASELINE config 5's read mix (100 / 150 bp, half of the bases each) through ragged leaves."""
-    d = run_bench([sys.executable, "bench.py", "--workload", "mixed", "--reads", "150000", "--steps", "1", "--warmup", "1", "--cpu-sample-reads", "10000",
+    d = run_bench([sys.executable, "bench.py", "--full", "--workload", "mixed", "--reads", "150000", "--steps", "1", "--warmup", "1", "--cpu-sample-reads", "10000",
                    "--no-host"])
     assert d["verified"] is True and d["cpu_baseline"]["gpu_parity_on_sample"] is True
     assert d["config"]["bases"][0] == 150000 // 5 * (3 * 101 + 2 * 151)
@@ -122,7 +138,7 @@ def test_bench_mixed_read_lengths(bwtm):
 
 def test_bench_distributed_path_on_one_rank(bwtm):
     d = run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                   "--master-port", "29517", "bench.py", "--gpus", "1", "--force-dist", "--reads", "200000", "--steps", "2", "--warmup", "1",
+                   "--master-port", "29517", "bench.py", "--full", "--gpus", "1", "--force-dist", "--reads", "200000", "--steps", "2", "--warmup", "1",
                    "--no-cpu-baseline"])
     assert d["value"] > 0 and d["config"]["native_bytes"][2] > 0 and d["verified"] is True and d["rccl_ranks"] == 1
     ph = d["sharded_phases_rank0"]                                  # what a SCALE line carries: phases of the sharded merge and the exchanged bytes
@@ -134,7 +150,7 @@ def test_bench_distributed_path_on_one_rank(bwtm):
 def test_bench_partitioned_on_one_rank(bwtm):
     """The merge over partitioned records as the bench runs it, on its one rank: a group of one, the part's windows transcoded from its resident
     byte share, pulled tables, the second half; the slice equals the single-GPU stream."""
-    d = run_bench([sys.executable, "bench.py", "--force-dist", "--search", "partitioned", "--reads", "3000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--force-dist", "--search", "partitioned", "--reads", "3000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
     assert d["verified"] is True and d["config"]["search"] == "partitioned" and d["value"] > 0 and d["rccl_ranks"] == 1
     ph = d["partitioned_phases_rank0"]
     assert ph["lf_steps"] + ph["node_levels"] == 101 and ph["ms_search"] > 0 and ph["ms_finish"] > 0 and ph["elements_advanced"] > 0
@@ -147,7 +163,7 @@ def test_bench_partitioned_between_processes_on_one_gpu(bwtm):
     """Three RANKS (processes started by bench.py itself) that share GPU 0: every rank is one part, maps the other ranks' exported buffers through
     HIP IPC handles and reads its share of every step's elements out of them; every rank's slice equals the same bytes of the single-GPU
     stream.  The process group is gloo (RCCL refuses several ranks on one device): the data path needs no collective library."""
-    cmd = [sys.executable, "bench.py", "--gpus", "3", "--same-device", "--search", "partitioned", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "3", "--same-device", "--search", "partitioned", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
     d = run_bench_shared_gpu(cmd)
     assert d["n_gpus"] == 3 and d["ranks"] == 3 and d["process_group"] == "gloo" and d["rccl_ranks"] is None
     assert d["verified"] is True and d["verification"]["slices"] == 3 and d["config"]["same_device"] is True
@@ -160,7 +176,7 @@ def test_bench_partitioned_under_the_drivers_launcher_on_one_gpu(bwtm):
     """The same with the ranks started the way the driver starts them (python -m torch.distributed.run ... bench.py --gpus N): nothing of bench.py's
     own launcher is in the environment, and the ranks still meet in one group (rank 0 makes the shared-memory name up, the process group carries it)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29519",
-           "bench.py", "--gpus", "2", "--same-device", "--search", "partitioned", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host"]
+           "bench.py", "--full", "--gpus", "2", "--same-device", "--search", "partitioned", "--reads", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host"]
     d = run_bench_shared_gpu(cmd)
     assert d["n_gpus"] == 2 and d["ranks"] == 2 and d["verified"] is True and d["config"]["search"] == "partitioned" and d["config"]["partitioned_fallback"] is None
 
@@ -168,7 +184,7 @@ def test_bench_partitioned_under_the_drivers_launcher_on_one_gpu(bwtm):
 def test_bench_chained_merge_of_four_sets(bwtm):
     """BASELINE config 5's shape: four sets of mixed 100 / 150 bp reads merged in command-line order, intermediate results
     device-resident; reads extracted from the final index equal the four generators'."""
-    d = run_bench([sys.executable, "bench.py", "--chain", "4", "--workload", "mixed", "--reads", "60000", "--steps", "1", "--warmup", "1",
+    d = run_bench([sys.executable, "bench.py", "--full", "--chain", "4", "--workload", "mixed", "--reads", "60000", "--steps", "1", "--warmup", "1",
                    "--no-cpu-baseline", "--verify-reads", "4000"])
     assert d["verified"] is True and len(d["config"]["bases"]) == 4
     h = d["host_to_host"]                               # the chain from page-locked inputs to a page-locked result, with and without announced uploads
@@ -187,10 +203,10 @@ def test_bench_two_gpus_self_launched(bwtm):
     ranks, every rank's output slice equals the same bytes of the single-GPU stream.  Runs wherever two GPUs are visible."""
     if _gpus() < 2:
         pytest.skip("needs two GPUs")
-    d = run_bench([sys.executable, "bench.py", "--gpus", "2", "--reads", "4000000", "--steps", "2", "--warmup", "1"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--gpus", "2", "--reads", "4000000", "--steps", "2", "--warmup", "1"])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["verified"] is True and d["value"] > 0
     assert d["verification"]["slices"] == 2 and d["cpu_baseline"] is None and d["config"]["search"] == "partitioned"
-    d = run_bench([sys.executable, "bench.py", "--gpus", "2", "--search", "blocks", "--reads", "4000000", "--steps", "2", "--warmup", "1", "--no-host"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--gpus", "2", "--search", "blocks", "--reads", "4000000", "--steps", "2", "--warmup", "1", "--no-host"])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["verified"] is True and d["config"]["search"] == "blocks"
 
 
