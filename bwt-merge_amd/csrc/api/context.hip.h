@@ -91,6 +91,7 @@ struct Tuning
 #ifdef BWTM_EXPERIMENTAL
   long long search_view = 0;              // the frontier search reads the two-plane search view: 0 = never (default: it saves 14 % of the HBM reads and no time), 1 = always, 2 = by size
 #endif
+  long long frontier_stage_out = 1;       // k_frontier_step stores the next frontier: 1 = in slot order through LDS (whole lines per wave), 0 = every lane its own element (rounds 1 - 6); changes the kernel's HBM traffic
   long long frontier_parts = 0;           // > 1: every step of the frontier search as this many launches over slices of the frontier (a measurement, same results)
   long long part_capacity = 0;            // tests: elements a part of the partitioned merge can hold in a step (0 = 2 m / parts + slack): forces the out-of-room
                                           // paths; negative: only the element steps are held to |value| (the roots and the expansion of the node levels are not)
@@ -266,6 +267,10 @@ void profile_collect()
 #define LAUNCH(name, kernel, grid, block, ...) LAUNCH_CFG(name, kernel, grid, 1, block, 0, __VA_ARGS__)
 #define LAUNCH_LDS(name, kernel, grid, block, lds, ...) LAUNCH_CFG(name, kernel, grid, 1, block, lds, __VA_ARGS__)
 #define LAUNCH2D(name, kernel, gridx, gridy, block, ...) LAUNCH_CFG(name, kernel, gridx, gridy, block, 0, __VA_ARGS__)
+// k_frontier_step<EMIT, HI, VIEW, PULL, STAGE>: the form of its stores is chosen per launch (g_tune.frontier_stage_out)
+#define LAUNCH_STEP(name, EMIT, HI, VIEW, PULL, grid, ...) do { \
+  if(g_tune.frontier_stage_out) { LAUNCH(name, (k_frontier_step<EMIT, HI, VIEW, PULL, true>), grid, FR_BLOCK, __VA_ARGS__); } \
+  else { LAUNCH(name, (k_frontier_step<EMIT, HI, VIEW, PULL, false>), grid, FR_BLOCK, __VA_ARGS__); } } while(0)
 
 //------------------------------------------------------------------------------
 // Pool.
@@ -634,6 +639,7 @@ int tune_set(const char* key, long long value)
 #ifdef BWTM_EXPERIMENTAL
   else if(k == "search_view") { g_tune.search_view = (value >= 0 && value <= 2 ? value : 0); }
 #endif
+  else if(k == "frontier_stage_out") { g_tune.frontier_stage_out = (value != 0); }
   else if(k == "frontier_parts") { g_tune.frontier_parts = (value > 0 ? value : 0); }
   else if(k == "ingest_verify") { g_tune.ingest_verify = (value != 0); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }

@@ -747,8 +747,8 @@ int part_search(PartSearch& S)
     f.bound_row = S.bound.as<u32>() + S.in_epoch * (S.ntiles + 1) - S.tile_first; f.step = S.in_epoch; f.block_base = 0;      // indexed by absolute tile numbers
     f.src_lo = S.srcs.as<const uint2* const>() + (2 * par + 0) * PART_MAX; f.src_hi = S.srcs.as<const unsigned short* const>() + (2 * par + 1) * PART_MAX;
     f.nseg_in = nseg_in;
-    if(S.wide) { LAUNCH("frontier_step", (k_frontier_step<0, true, false, true>), grid, FR_BLOCK, S.A->view(), S.B->view(), f); }
-    else { LAUNCH("frontier_step", (k_frontier_step<0, false, false, true>), grid, FR_BLOCK, S.A->view(), S.B->view(), f); }
+    if(S.wide) { LAUNCH_STEP("frontier_step", 0, true, false, true, grid, S.A->view(), S.B->view(), f); }
+    else { LAUNCH_STEP("frontier_step", 0, false, false, true, grid, S.A->view(), S.B->view(), f); }
     nb_out = grid; par = 1 - par;
     S.in_epoch++; S.epoch_used += n_in;
     P->info.steps = t + 1; P->info.elements += n_in; if(n_in > P->info.largest) { P->info.largest = n_in; }

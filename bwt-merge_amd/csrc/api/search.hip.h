@@ -483,8 +483,8 @@ int search_frontier(const bwtm_index* a, const bwtm_index* b, u64 seq_first, u64
     f.emit16 = emit16.as<unsigned short>(); f.emit_base = emit_base.as<const u64>(); f.emit_cap = emit_cap; f.bits32 = ra->bits_as<u32>();
     f.bound_row = bound.as<u32>() + in_epoch * (ntiles + 1); f.step = in_epoch; f.block_base = 0; f.src_lo = nullptr; f.src_hi = nullptr; f.nseg_in = 0;
 #ifdef BWTM_DIAGNOSTICS
-    if(g_tune.walk_emit == 1 && wide) { LAUNCH("frontier_step_noemit", (k_frontier_step<1, true>), grid, FR_BLOCK, a->view(), b->view(), f); }
-    else if(g_tune.walk_emit == 1) { LAUNCH("frontier_step_noemit", (k_frontier_step<1, false>), grid, FR_BLOCK, a->view(), b->view(), f); }
+    if(g_tune.walk_emit == 1 && wide) { LAUNCH_STEP("frontier_step_noemit", 1, true, false, false, grid, a->view(), b->view(), f); }
+    else if(g_tune.walk_emit == 1) { LAUNCH_STEP("frontier_step_noemit", 1, false, false, false, grid, a->view(), b->view(), f); }
     else
 #endif
     if(g_tune.frontier_parts > 1)
@@ -497,16 +497,16 @@ int search_frontier(const bwtm_index* a, const bwtm_index* b, u64 seq_first, u64
         f.block_base = (u32)(part * per);
         const u64 nb_part = std::min<u64>(per, nb_max - part * per);
         const char* label = (part == 0 ? "frontier_step_slice0" : "frontier_step_slices");
-        if(wide) { LAUNCH(label, (k_frontier_step<0, true>), nb_part, FR_BLOCK, a->view(), b->view(), f); }
-        else { LAUNCH(label, (k_frontier_step<0, false>), nb_part, FR_BLOCK, a->view(), b->view(), f); }
+        if(wide) { LAUNCH_STEP(label, 0, true, false, false, nb_part, a->view(), b->view(), f); }
+        else { LAUNCH_STEP(label, 0, false, false, false, nb_part, a->view(), b->view(), f); }
       }
     }
 #ifdef BWTM_EXPERIMENTAL
-    else if(use_view && wide) { LAUNCH("frontier_step", (k_frontier_step<0, true, true>), grid, FR_BLOCK, a->view(), b->view(), f); }
-    else if(use_view) { LAUNCH("frontier_step", (k_frontier_step<0, false, true>), grid, FR_BLOCK, a->view(), b->view(), f); }
+    else if(use_view && wide) { LAUNCH_STEP("frontier_step", 0, true, true, false, grid, a->view(), b->view(), f); }
+    else if(use_view) { LAUNCH_STEP("frontier_step", 0, false, true, false, grid, a->view(), b->view(), f); }
 #endif
-    else if(wide) { LAUNCH("frontier_step", (k_frontier_step<0, true>), grid, FR_BLOCK, a->view(), b->view(), f); }
-    else { LAUNCH("frontier_step", (k_frontier_step<0, false>), grid, FR_BLOCK, a->view(), b->view(), f); }
+    else if(wide) { LAUNCH_STEP("frontier_step", 0, true, false, false, grid, a->view(), b->view(), f); }
+    else { LAUNCH_STEP("frontier_step", 0, false, false, false, grid, a->view(), b->view(), f); }
     // the size of step t reaches the host behind step t's kernels: recorded AFTER the step kernel, so that reduce, scan and step
     // follow each other without another command between them
     if(size_in_ring) { HIP_TRY(hipEventRecord(events.ev[t % LOOK], CTX.stream)); }

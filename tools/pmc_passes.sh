@@ -12,6 +12,7 @@ i=0
 for set in "${sets[@]}"; do
   i=$((i+1)); rm -rf /tmp/pmc_$i
   timeout 900 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_$i -- python3 $R/bench.py $PMC_BENCH_ARGS --no-cpu-baseline --no-verify --no-host --target off --steps 1 --warmup 0 > /tmp/pmc_$i.log 2>&1
+  rc=$?
   f=$(find /tmp/pmc_$i -name "*counter_collection.csv" | head -1)
-  if [ -n "$f" ]; then python3 $R/tools/pmc_aggregate.py $f >> $out/pmc.txt; else echo "pass $i ($set) failed" >> $out/pmc.txt; tail -5 /tmp/pmc_$i.log >> $out/pmc.txt; fi
+  if [ $rc -eq 0 ] && [ -n "$f" ]; then python3 $R/tools/pmc_aggregate.py $f >> $out/pmc.txt; else echo "pass $i ($set) failed with status $rc: no further pass is started" >> $out/pmc.txt; grep -v "bench\] input" /tmp/pmc_$i.log | tail -40 >> $out/pmc.txt; exit 1; fi
 done
