@@ -405,8 +405,8 @@ def test_find_batch_matches_oracle_backward_search(gpu, oracle):
 
 def test_mid_size_properties_merge_tree_associativity(gpu, oracle):
     """Size-independent properties at a size the brute force cannot reach (2 x 3e5 reads = 60 Mbase):
-    the same collection merged along different trees gives the same bytes, the counts add up, and
-    reads extracted from the merged index by LF walk equal the generator's."""
+    the same collection merged along different trees gives the same bytes, the counts add up,
+    reads extracted from the merged index by LF walk equal the generator's, and the whole stream inverts to all of the generator's reads."""
     import torch
     from bwt_merge_amd import synth
     dev = torch.device("cuda", 0)
@@ -438,6 +438,11 @@ def test_mid_size_properties_merge_tree_associativity(gpu, oracle):
     for j, seq in zip(ids, got):
         seed, idx = (1001, int(j)) if j < n else (1002, int(j - n))
         assert seq == synth.generate_reads(seed, idx, 1, L)[0].tolist()
+    # ... and ALL reads do: the stream, its samples and C are the BWT of the 600 000 generated reads in order, by inversion on the host
+    # (tests/bwt_certificate.py), so the two trees do not merely agree, both are right
+    from bwt_certificate import certify_native
+    reads = np.concatenate([synth.generate_reads(seed, 0, n, L).numpy() for seed in (1001, 1002)])
+    assert certify_native(oracle, d1, m1.sequences, m1.bases, be1, cum1, m1.C, reads) is None
 
 
 def test_sharded_search_with_caller_owned_buffers(gpu, oracle):
