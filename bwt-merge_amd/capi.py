@@ -132,6 +132,7 @@ SYMBOLS = [
     ("bwtm_builder_finish", C.c_int, [vp, C.POINTER(vp)]),
     ("bwtm_builder_free", None, [vp]),
     ("bwtm_pool_stats", C.c_int, [vp]),
+    ("bwtm_pool_poison_stats", C.c_int, [p_u64, p_u64]),
     ("bwtm_group_create", C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]),
     ("bwtm_group_free", None, [vp]),
     ("bwtm_group_part", C.c_int, [vp]),
@@ -965,6 +966,13 @@ def pool_stats():
     info = PoolInfo()
     check(lib().bwtm_pool_stats(C.byref(info)))
     return {k: int(getattr(info, k)) for k, _ in PoolInfo._fields_}
+
+
+def pool_poison_stats():
+    """(fills, bytes) of the poison mode (BWTM_POOL_POISON in the environment), process-wide; (0, 0) when it is off."""
+    fills, nbytes = u64(0), u64(0)
+    check(lib().bwtm_pool_poison_stats(C.byref(fills), C.byref(nbytes)))
+    return int(fills.value), int(nbytes.value)
 
 
 def profile_enable(on=True):

@@ -329,8 +329,39 @@ struct AddressSpace
 AddressSpace g_va;
 u64 VA_SEGMENT = 8ull << 40, VA_LIMIT = 64ull << 40;        // BWTM_POOL_VA_SEGMENT / BWTM_POOL_VA_LIMIT (bytes) override them: the tests exhaust a small range
 
+// BWTM_POOL_POISON=<32-bit word, decimal or 0x...> (a test hook, off by default): every block the library hands itself -- pool_get, recycled or
+// new, over its whole size, and the parts' exported arena on every return of group_arena -- is filled with that word before its user sees
+// it, so that a kernel that reads bytes nobody wrote computes with the poison, not with zeros of a fresh hipMalloc or the right bytes of the
+// previous buffer of the same size.  bwtm_pool_poison_stats() counts the fills (process-wide): a test proves with it that the mode was on.
+bool POOL_POISON = false;
+u32 POOL_POISON_WORD = 0;
+std::atomic<u64> g_poison_fills{0}, g_poison_bytes{0};
+
+// `bytes` is a multiple of 4 (pool blocks are multiples of 256 bytes).  The fill is followed by a synchronisation: blocks are also filled
+// from the copy stream (chunked uploads), which is not ordered behind the compute stream; in this mode simplicity beats speed.
+hipError_t pool_poison_fill(bwtm_context* c, void* p, u64 bytes, const char* what)
+{
+  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)p, (int)POOL_POISON_WORD, bytes / 4, c->stream);
+  if(e == hipSuccess) { e = hipStreamSynchronize(c->stream); }
+  if(e != hipSuccess) { return e; }
+  g_poison_fills.fetch_add(1, std::memory_order_relaxed); g_poison_bytes.fetch_add(bytes, std::memory_order_relaxed);
+  if(trace_enabled()) { fprintf(stderr, "[bwtm] poison %s %p: %llu bytes of 0x%08X\n", what, p, (unsigned long long)bytes, POOL_POISON_WORD); }
+  return hipSuccess;
+}
+
 void vmm_setup(bwtm_context* c)
 {
+  static const bool poison_read = []()                       // once per process, before the first context's first block
+  {
+    const char* v = std::getenv("BWTM_POOL_POISON");
+    if(!v) { return true; }
+    char* end = nullptr;
+    const u64 x = std::strtoull(v, &end, 0);
+    if(end != v && *end == 0 && x <= 0xFFFFFFFFull) { POOL_POISON_WORD = (u32)x; POOL_POISON = true; }
+    else { fprintf(stderr, "[bwtm] BWTM_POOL_POISON=%s is not a 32-bit value: ignored\n", v); }
+    return true;
+  }();
+  (void)poison_read;
   const char* env = std::getenv("BWTM_POOL_VMM");
   if(env && env[0] == '0') { return; }
   if(const char* v = std::getenv("BWTM_POOL_VMM_CHUNK")) { u64 x = std::strtoull(v, nullptr, 10); if(x >= (2ull << 20)) { VMM_CHUNK = x / (2ull << 20) * (2ull << 20); } }
@@ -467,7 +498,9 @@ void pool_trim(bwtm_context* c)
   if(trace_enabled()) { fprintf(stderr, "[bwtm] trim: %zu blocks, %.2f GB, %.1f ms\n", blocks, bytes / 1e9, trace_now() - t0); }
 }
 
-hipError_t pool_get(bwtm_context* c, u64 n, void** p, u64* actual)
+void pool_put(bwtm_context* c, void* p, u64 n);
+
+hipError_t pool_take(bwtm_context* c, u64 n, void** p, u64* actual)
 {
   n = pool_round(n);
   const bool large = (c->vmm && n >= VMM_MIN);
@@ -496,6 +529,18 @@ hipError_t pool_get(bwtm_context* c, u64 n, void** p, u64* actual)
   if(e != hipSuccess) { (void)hipGetLastError(); pool_trim(c); e = hipMalloc(p, n); }
   if(e == hipSuccess) { c->held_bytes += n; if(c->held_bytes > c->peak_bytes) { c->peak_bytes = c->held_bytes; } }
   if(e == hipSuccess && g_va.exhausted && n >= VMM_MIN) { c->va_fallbacks++; }      // a large block that should have been a mapped one
+  return e;
+}
+
+// A block of at least n bytes (*actual: its size), recycled or new.
+hipError_t pool_get(bwtm_context* c, u64 n, void** p, u64* actual)
+{
+  hipError_t e = pool_take(c, n, p, actual);
+  if(e == hipSuccess && POOL_POISON)
+  {
+    e = pool_poison_fill(c, *p, *actual, "block");
+    if(e != hipSuccess) { pool_put(c, *p, *actual); }
+  }
   return e;
 }
 
@@ -729,6 +774,13 @@ extern "C" int bwtm_pool_stats(bwtm_pool_info* info)
     std::lock_guard<std::mutex> lock(g_va.mu);
     info->address_bytes_reserved = g_va.reserved_total; info->address_space_exhausted = (g_va.exhausted ? 1 : 0);
   }
+  return BWTM_OK;
+}
+
+extern "C" int bwtm_pool_poison_stats(uint64_t* fills, uint64_t* bytes)
+{
+  if(fills) { *fills = g_poison_fills.load(); }
+  if(bytes) { *bytes = g_poison_bytes.load(); }
   return BWTM_OK;
 }
 

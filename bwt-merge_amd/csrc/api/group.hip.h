@@ -172,12 +172,23 @@ int group_pinned(bwtm_group* g, char** out)
   return BWTM_OK;
 }
 
-// This part's exported arena: at least `bytes`, zeroed where `zero_bytes` says (from its start); re-published when it had to grow.
+// BWTM_POOL_POISON: the arena is filled on every return of group_arena, the reused block included.  No peer reads it at these points: the
+// callers (search_setup and part_finish, api/pmerge.hip.h) come behind an all-gather that every part enters only after its last kernel that
+// reads a peer's arena has completed (the search's last exchange; the range counts of the previous merge's finish), and before the first
+// all-gather or barrier behind which a peer reads what this merge writes into it.
+int group_arena_poison(bwtm_group* g)
+{
+  if(!POOL_POISON) { return BWTM_OK; }
+  HIP_TRY(pool_poison_fill(t_ctx, g->arena, g->arena_bytes, "arena"));
+  return BWTM_OK;
+}
+
+// This part's exported arena: at least `bytes`, contents undefined; re-published when it had to grow.
 int group_arena(bwtm_group* g, u64 bytes, void** out)
 {
   int device = 0;
   HIP_TRY(hipGetDevice(&device));
-  if(g->arena && g->arena_bytes >= bytes && g->arena_device == device) { *out = g->arena; return BWTM_OK; }
+  if(g->arena && g->arena_bytes >= bytes && g->arena_device == device) { *out = g->arena; return group_arena_poison(g); }
   if(g->arena)
   {
     // peers may still hold the old block mapped: it is only released here after every part has passed a barrier in the new merge's
@@ -199,7 +210,7 @@ int group_arena(bwtm_group* g, u64 bytes, void** out)
   }
   a.generation.store(a.generation.load() + 1, std::memory_order_release);
   *out = g->arena;
-  return BWTM_OK;
+  return group_arena_poison(g);
 }
 
 // Part h's arena as this part addresses it (after a barrier behind h's group_arena call).

@@ -448,6 +448,10 @@ typedef struct
   uint64_t hipmalloc_fallbacks;                       /* large blocks served by hipMalloc since then */
 } bwtm_pool_info;
 int bwtm_pool_stats(bwtm_pool_info* info);
+/* A test hook.  BWTM_POOL_POISON=<32-bit value, decimal or 0x...> in the environment (read once per process): every block of device memory
+   the library hands itself is filled with that word before it is used, so that bytes no kernel wrote are never zeros or leftovers by luck.
+   Reports the fills made so far and the bytes they covered, process-wide (NULL: not wanted); both stay 0 when the mode is off. */
+int bwtm_pool_poison_stats(uint64_t* fills, uint64_t* bytes);
 
 /* --- measurement ----------------------------------------------------------------------------- */
 
