@@ -35,6 +35,22 @@ class HostOutput(C.Structure):
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, u64)
 
 
+class Piece(C.Structure):
+    """bwtm_piece"""
+    _fields_ = [("byte_first", u64), ("nbytes", u64), ("data", C.c_void_p), ("sample_block_first", u64), ("sample_blocks", u64),
+                ("sample_width", C.c_int), ("fields", C.c_void_p), ("anchors", C.c_void_p), ("anchor_first", u64), ("nanchors", u64),
+                ("block_end", C.c_void_p), ("cum", C.c_void_p), ("last", C.c_int)]
+
+
+class StreamStats(C.Structure):
+    """bwtm_stream_stats"""
+    _fields_ = [("pieces", u64), ("slice_records", u64), ("slice_bytes_peak", u64),
+                ("ms_upload", C.c_double), ("ms_search", C.c_double), ("ms_second_half", C.c_double), ("ms_total", C.c_double)]
+
+
+PIECE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Piece))
+
+
 class HostIndex(C.Structure):
     """bwtm_host_index"""
     _fields_ = [("data", C.c_void_p), ("nbytes", u64), ("blocks", u64), ("sequences", u64), ("bases", u64), ("C", u64 * (SIGMA + 1)), ("cum", C.c_void_p)]
@@ -85,6 +101,8 @@ SYMBOLS = [
     ("bwtm_merge_host_chained", C.c_int, [vp, C.POINTER(HostInput), ALLOC_FN, vp, C.c_int, C.POINTER(HostOutput), C.POINTER(vp)]),
     ("bwtm_merge_host_pipelined", C.c_int, [vp, C.POINTER(HostInput), C.POINTER(HostInput), vp, C.POINTER(HostInput), C.POINTER(vp), ALLOC_FN, vp, C.c_int,
                                             C.POINTER(HostOutput), C.POINTER(vp)]),
+    ("bwtm_merge_host_streamed", C.c_int, [vp, C.POINTER(HostInput), C.POINTER(HostInput), u64, C.c_int, PIECE_FN, vp, C.POINTER(HostOutput),
+                                           C.POINTER(StreamStats)]),
     ("bwtm_upload_begin", C.c_int, [C.POINTER(HostInput), C.POINTER(vp)]),
     ("bwtm_upload_finish", C.c_int, [vp, C.POINTER(vp)]),
     ("bwtm_upload_free", None, [vp]),
@@ -359,6 +377,126 @@ def merge_host(a, b, samples=True, keep=False, chained=None, buffers=None):
 
 
 RESULT_ON_DEVICE = -1
+
+
+def _copy_from(ptr, count, dtype):
+    """A numpy copy of `count` items at a C address (the library's staging is only valid until the sink returns)."""
+    if not ptr or count == 0:
+        return np.zeros(0, dtype=dtype)
+    nbytes = count * np.dtype(dtype).itemsize
+    return np.frombuffer((C.c_uint8 * nbytes).from_address(ptr), dtype=dtype).copy()
+
+
+class PieceCopy:
+    """The contents of one bwtm_piece, copied out of the library's staging."""
+
+    def __init__(self, piece):
+        self.byte_first, self.nbytes = int(piece.byte_first), int(piece.nbytes)
+        self.sample_block_first, self.sample_blocks = int(piece.sample_block_first), int(piece.sample_blocks)
+        self.sample_width, self.last = int(piece.sample_width), bool(piece.last)
+        self.anchor_first, self.nanchors = int(piece.anchor_first), int(piece.nanchors)
+        ns = self.sample_blocks
+        self.data = _copy_from(piece.data, self.nbytes, np.uint8)
+        self.fields = self.anchors = self.block_end = self.cum = None
+        if ns > 0 and self.sample_width in FIELD_DTYPES:
+            self.fields = _copy_from(piece.fields, SIGMA * ns, FIELD_DTYPES[self.sample_width]).reshape(SIGMA, ns)
+            self.anchors = _copy_from(piece.anchors, SIGMA * self.nanchors, np.uint64).reshape(SIGMA, self.nanchors)
+        elif ns > 0 and self.sample_width == 8:
+            self.block_end = _copy_from(piece.block_end, ns, np.uint64)
+            self.cum = _copy_from(piece.cum, SIGMA * ns, np.uint64).reshape(SIGMA, ns)
+
+
+def assemble_pieces(pieces, C_array):
+    """The pieces of a streamed merge laid end to end: (data, width, fields, anchors) with the fields widened to the largest width of any
+    piece -- what bwtm_index_download_samples_compact gives for the whole result --, or (data, 8, block_end, cum[6][blocks + 1]) as
+    bwtm_index_download_samples gives them (the column behind the last block comes from C), or (data, 0, None, None) without samples.
+    A pure function of the pieces (objects with PieceCopy's attributes); raises BwtmError when they do not fit together."""
+    if not pieces or [bool(p.last) for p in pieces].count(True) != 1 or not pieces[-1].last:
+        raise BwtmError("streamed merge: exactly the final piece must be marked last")
+    at_byte = at_block = 0
+    for p in pieces:
+        if p.byte_first != at_byte or (p.sample_blocks > 0 and p.sample_block_first != at_block):
+            raise BwtmError("streamed merge: piece at byte %d / block %d, expected %d / %d" % (p.byte_first, p.sample_block_first, at_byte, at_block))
+        at_byte += p.nbytes
+        at_block += p.sample_blocks
+    data = np.concatenate([p.data for p in pieces]) if pieces else np.zeros(0, dtype=np.uint8)
+    sampled = [p for p in pieces if p.sample_blocks > 0]
+    width = max([p.sample_width for p in pieces])
+    if width == 0:
+        return data, 0, None, None
+    blocks = at_block
+    if width != 8:
+        dtype = FIELD_DTYPES[width]
+        fields = np.concatenate([p.fields.astype(dtype) for p in sampled], axis=1) if sampled else np.zeros((SIGMA, 0), dtype=dtype)
+        at_anchor = 0
+        for p in sampled:
+            if p.nanchors != (p.sample_block_first + p.sample_blocks + 63) // 64 - (p.sample_block_first + 63) // 64 or (p.nanchors > 0 and p.anchor_first != at_anchor):
+                raise BwtmError("streamed merge: a piece's anchors do not continue those of the pieces before it")
+            at_anchor += p.nanchors
+        anchors = np.concatenate([p.anchors for p in sampled], axis=1) if sampled else np.zeros((SIGMA, 0), dtype=np.uint64)
+        return data, width, fields, anchors
+    # the full arrays; compact pieces among them (a compact-mode merge in which one piece held a block of 2^32 - 1 positions or more) are
+    # expanded from the back: the position and counts behind the last block are C's, and a piece ends where the next one starts
+    C_array = np.asarray(C_array, dtype=np.uint64)
+    totals = C_array[1: SIGMA + 1] - C_array[:SIGMA]
+    end = np.concatenate([C_array[SIGMA: SIGMA + 1], totals[1:]])   # start position and counts of 1..5 behind the piece
+    block_end, cum = [], []
+    for p in reversed(sampled):
+        if p.sample_width == 8:
+            block_end.append(p.block_end); cum.append(p.cum)
+            end = np.concatenate([p.cum[:, :1].sum(axis=0, dtype=np.uint64), p.cum[1:, 0]])
+            continue
+        f = p.fields.astype(np.uint64)
+        start = end - f.sum(axis=1, dtype=np.uint64)
+        at = start[:, None] + (np.cumsum(f, axis=1, dtype=np.uint64) - f)
+        block_end.append(at[0] + f[0] - np.uint64(1))
+        full = at.copy(); full[0] = at[0] - at[1:].sum(axis=0, dtype=np.uint64)
+        cum.append(full)
+        end = start
+    block_end.reverse(); cum.reverse()
+    return (data, 8, np.concatenate(block_end) if block_end else np.zeros(0, dtype=np.uint64),
+            np.concatenate(cum + [totals.reshape(SIGMA, 1)], axis=1))
+
+
+SAMPLES_NONE, SAMPLES_FULL, SAMPLES_COMPACT = 0, 1, 2
+
+
+def merge_host_streamed(a, b, slice_records=0, samples=SAMPLES_COMPACT, chained=None, sink=None):
+    """bwtm_merge_host_streamed: the merged BWT leaves the device slice by slice (slice_records records each, 0 = the library chooses).
+    a, b: (data uint8 array, sequences, bases); chained: a device Index (consumed) instead of a.
+    sink(PieceCopy) -> falsy to go on, truthy to stop (the call then raises BwtmError); given a sink, the call returns (out, stats).
+    Without one the pieces are collected and the call returns (data, width, fields, anchors, out, stats) -- or (data, 8, block_end,
+    cum, out, stats) with the full samples, (data, 0, None, None, out, stats) without samples -- assembled by assemble_pieces."""
+    pieces = []
+    failure = []
+
+    def on_piece(user, piece):
+        try:
+            pc = PieceCopy(piece.contents)
+            if sink is None:
+                pieces.append(pc)
+                return 0
+            return 1 if sink(pc) else 0
+        except BaseException as e:               # an exception must not unwind through the C frames
+            failure.append(e)
+            return 2
+
+    cb = PIECE_FN(on_piece)
+    out, stats = HostOutput(), StreamStats()
+    hb = _host_input(*b)
+    if chained is not None:
+        h, chained.h = chained.h, None                     # consumed by the call
+        rc = lib().bwtm_merge_host_streamed(h, None, C.byref(hb), int(slice_records), int(samples), cb, None, C.byref(out), C.byref(stats))
+    else:
+        ha = _host_input(*a)
+        rc = lib().bwtm_merge_host_streamed(None, C.byref(ha), C.byref(hb), int(slice_records), int(samples), cb, None, C.byref(out), C.byref(stats))
+    if failure:
+        raise failure[0]
+    check(rc)
+    if sink is not None:
+        return out, stats
+    data, width, x, y = assemble_pieces(pieces, list(out.C))
+    return data, width, x, y, out, stats
 
 
 class Upload:

@@ -64,6 +64,10 @@ struct bwtm_context
 
   // small page-locked scratch for results read back by the host (a pageable destination would make
   // hipMemcpyAsync stage and block)
+  // page-locked staging of bwtm_merge_host_streamed (two sets of bytes + samples), kept between calls: pinning 100 MB takes ~10 ms,
+  // which a call of ~500 ms would pay four times; returned by bwtm_trim and with the context
+  void* stream_stage[4] = {nullptr, nullptr, nullptr, nullptr};
+  u64 stream_stage_cap[4] = {0, 0, 0, 0};
   u64* host_scratch = nullptr;             // 128 u64: [0, 32) call results, [32, 64) upload / encode / slices, [64, 96) the search's size ring
   // The one-launch scans (k_frontier_scan1, k_pull_scan1) let a tile wait for the tiles before it: all their workgroups must be resident at the
   // same time.  The limits come from THIS device (CUs x workgroups of the kernel per CU, capped at FRONTIER_SCAN1_TILES); larger tables take the
@@ -97,6 +101,7 @@ struct Tuning
                                           // paths; negative: only the element steps are held to |value| (the roots and the expansion of the node levels are not)
   long long recs_uniform = 0;             // k_build_recs: the straight-line deposit for streams of longer runs: 1 always, -1 never, 0 = by the stream's density
   long long recs_window = 0;              // k_build_recs: positions per LDS window (8192 / 16384 / 32768); 0 = by the stream's density (A/B measurements)
+  long long stream_samples_query = 0;     // bwtm_merge_host_streamed: 1 = the samples' counts from one rank query per block start (k_block_cum_slice) instead of the encoder's cum32: the cross-check
   long long ingest_verify = 0;            // 1 = the builder checks every leaf's suffix order against the reads (one extra pass of gathers per leaf)
 #ifdef BWTM_DIAGNOSTICS
   long long walk_emit = 0;       // 0 = real emit; 1 / 2 timing-only variants of the emit (see diagnostics.hip.h)
@@ -123,6 +128,10 @@ thread_local bwtm_context* t_ctx = nullptr;          // the context of the API c
 
 void vmm_setup(bwtm_context* c);
 void pool_trim(bwtm_context* c);
+void stream_stage_free(bwtm_context* c)
+{
+  for(int k = 0; k < 4; k++) { if(c->stream_stage[k]) { (void)hipHostFree(c->stream_stage[k]); } c->stream_stage[k] = nullptr; c->stream_stage_cap[k] = 0; }
+}
 void apply_env_tuning();
 
 int context_setup(bwtm_context* c, int device)
@@ -166,6 +175,7 @@ void context_teardown(bwtm_context* c)
   for(auto& p : c->pending) { (void)hipEventDestroy(p.start); (void)hipEventDestroy(p.stop); }
   c->pending.clear();
   pool_trim(c);
+  stream_stage_free(c);
   if(c->host_scratch) { (void)hipHostFree(c->host_scratch); }
   if(c->stream) { (void)hipStreamDestroy(c->stream); }
   if(c->copy_stream) { (void)hipStreamDestroy(c->copy_stream); }
@@ -686,6 +696,7 @@ int tune_set(const char* key, long long value)
 #endif
   else if(k == "frontier_stage_out") { g_tune.frontier_stage_out = (value != 0); }
   else if(k == "frontier_parts") { g_tune.frontier_parts = (value > 0 ? value : 0); }
+  else if(k == "stream_samples_query") { g_tune.stream_samples_query = (value != 0); }
   else if(k == "ingest_verify") { g_tune.ingest_verify = (value != 0); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }
   else if(k == "recs_uniform") { g_tune.recs_uniform = (value > 0 ? 1 : (value < 0 ? -1 : 0)); }
@@ -744,6 +755,7 @@ extern "C" int bwtm_trim(void)
 {
   ENTER(nullptr);
   pool_trim(t_ctx);
+  stream_stage_free(t_ctx);
   return BWTM_OK;
 }
 

@@ -363,12 +363,14 @@ int encode_emit(bwtm_index* x, EncodePlan& plan, u8* host_out, bool with_cum = f
       if(with_cum)
       {
         LAUNCH("enc_emit", k_enc_emit<true>, div_up((s1 - s0) * WAVE, BLOCK_THREADS), BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, s0, s1,
-          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), x->cum32.as<u32>(), cum_stride);
+          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), x->cum32.as<u32>(), cum_stride,
+          (u64)0, 0u, (const u64*)nullptr);
       }
       else
       {
         LAUNCH("enc_emit", k_enc_emit<false>, div_up((s1 - s0) * WAVE, BLOCK_THREADS), BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, s0, s1,
-          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), (u32*)nullptr, (u64)0);
+          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), (u32*)nullptr, (u64)0,
+          (u64)0, 0u, (const u64*)nullptr);
       }
       return BWTM_OK;
     };

@@ -38,6 +38,18 @@ struct bwtm_slice
   DevBuf data;                         // bytes [byte_first & ~63, byte_end)
   u64 block_first = 0, nblocks = 0;    // blocks whose first byte lies in the slice: [block_first, block_first + nblocks)
   DevBuf block_start;                  // nblocks + 1 entries (the last one is filled in by download_samples)
+  DevBuf cum32;                        // 5 x nblocks u32 (kernels/encoder.hip.h), only when the encoder was asked for them (api/stream.hip.h)
+
+  // bwtm_merge_host_streamed: page-locked words (device-visible address, 72 u64) that the small results of the three calls below are STORED
+  // into by a kernel instead of copied (kernels/stream.hip.h, k_store_host); null: copies into the context's scratch
+  u64* host_direct = nullptr;
+  // device memory the slice owns now, and the most it owned since a caller last cleared the mark (the size tables live from
+  // bwtm_slice_size_table to the end of bwtm_slice_encode)
+  u64 bytes_high = 0;
+  u64 device_bytes() const
+  {
+    return recs.bytes + sup.bytes + lasthead.bytes + table.bytes + group_table.bytes + group_base.bytes + seg_base.bytes + data.bytes + block_start.bytes + cum32.bytes;
+  }
 
   const uint4* recs_virtual() const { return recs.as<const uint4>() - 4 * rec_halo; }
   u64 pos_first() const { return rec_first << REC_SHIFT; }
@@ -255,18 +267,24 @@ extern "C" int bwtm_slice_lasthead(bwtm_slice* s, uint64_t* lasthead)
     s->seg_first, s->seg_end, s->lasthead.as<u64>() - s->seg_first);
   // exclusive max-scan over nseg + 1 entries: entry k = (last head of the slice before its segment k) + 1, the extra entry = the slice's own
   TRY(device_scan<1>(s->lasthead.as<u64>(), s->lasthead.as<u64>(), nseg + 1));
-  TRY(fetch_u64(s->lasthead.as<u64>() + nseg, 0));
+  if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, s->lasthead.as<const u64>() + nseg, s->host_direct, 1u); }
+  else { TRY(fetch_u64(s->lasthead.as<u64>() + nseg, 0)); }
   // the symbol before the slice (for the samples of blocks opened by a run that began in an earlier slice)
   DevBuf sym; TRY(sym.alloc(8));
   if(s->rec_first > 0)
   {
     LAUNCH("extract", k_extract, 1, BLOCK_THREADS, s->view(), s->pos_first() - 1, (u64)1, sym.as<u8>());
-    CTX.host_scratch[1] = 0;
-    HIP_TRY(hipMemcpyAsync(CTX.host_scratch + 1, sym.p, 1, hipMemcpyDeviceToHost, CTX.stream));
+    if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, sym.as<const u64>(), s->host_direct + 1, 1u); }       // (8 bytes allocated, the first one written)
+    else
+    {
+      CTX.host_scratch[1] = 0;
+      HIP_TRY(hipMemcpyAsync(CTX.host_scratch + 1, sym.p, 1, hipMemcpyDeviceToHost, CTX.stream));
+    }
   }
   HIP_TRY(hipStreamSynchronize(CTX.stream));
-  *lasthead = CTX.host_scratch[0];
-  s->halo_symbol = (s->rec_first > 0 ? (u32)(CTX.host_scratch[1] & 0xFF) : 0u);
+  const u64* got = (s->host_direct ? s->host_direct : CTX.host_scratch);
+  *lasthead = got[0];
+  s->halo_symbol = (s->rec_first > 0 ? (u32)(got[1] & 0xFF) : 0u);
   return BWTM_OK;
 }
 
@@ -289,15 +307,18 @@ extern "C" int bwtm_slice_size_table(bwtm_slice* s, uint64_t heads_before, uint6
     s->lasthead.as<const u64>() - s->seg_first, heads_before, s->table.as<u32>() - s->seg_first * 64);
   LAUNCH("fold_group", k_fold_group, s->ngroups, WAVE, s->table.as<const u32>(), nseg, s->group_table.as<u64>());
   LAUNCH("fold_slice", k_fold_slice, 1, WAVE, s->group_table.as<const u64>(), s->ngroups, slice_table.as<u64>());
-  HIP_TRY(hipMemcpyAsync(table, slice_table.p, 64 * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+  if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, slice_table.as<const u64>(), s->host_direct + 8, 64u); }
+  else { HIP_TRY(hipMemcpyAsync(table, slice_table.p, 64 * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
   HIP_TRY(hipStreamSynchronize(CTX.stream));
+  if(s->host_direct) { for(int o = 0; o < 64; o++) { table[o] = s->host_direct[8 + o]; } }
   return BWTM_OK;
 }
 
-extern "C" int bwtm_slice_encode(bwtm_slice* s, uint64_t byte_offset)
+namespace
 {
-  if(!s) { return fail(BWTM_EINVAL, "bwtm_slice_encode: null argument"); }
-  ENTER(s->ctx);
+// with_cum: the encoder also writes the slice's cum32 (k_enc_emit<true, true>; needs halo_symbol, i.e. bwtm_slice_lasthead).
+int slice_encode(bwtm_slice* s, u64 byte_offset, bool with_cum)
+{
   if(s->stage < 2) { return fail(BWTM_EINVAL, "bwtm_slice_encode: call bwtm_slice_size_table first"); }
   const u64 nseg = s->seg_end - s->seg_first;
   s->byte_first = byte_offset; s->byte_end = byte_offset;
@@ -309,25 +330,46 @@ extern "C" int bwtm_slice_encode(bwtm_slice* s, uint64_t byte_offset)
     TRY(s->seg_base.alloc(nseg * sizeof(u64)));
     LAUNCH("fold_top", k_fold_top, 1, WAVE, s->group_table.as<const u64>(), s->ngroups, byte_offset, s->group_base.as<u64>());
     LAUNCH("fold_seg", k_fold_seg, s->ngroups, WAVE, s->table.as<const u32>(), nseg, s->group_base.as<const u64>(), s->seg_base.as<u64>());
-    TRY(fetch_u64(s->group_base.as<u64>() + s->ngroups, 0));
+    if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, s->group_base.as<const u64>() + s->ngroups, s->host_direct, 1u); }
+    else { TRY(fetch_u64(s->group_base.as<u64>() + s->ngroups, 0)); }
     HIP_TRY(hipStreamSynchronize(CTX.stream));
-    s->byte_end = CTX.host_scratch[0];
+    s->byte_end = (s->host_direct ? s->host_direct[0] : CTX.host_scratch[0]);
     const u64 base = byte_offset & ~(u64)(RLE_BLOCK - 1);
     s->block_first = div_up(byte_offset, RLE_BLOCK);
     s->nblocks = div_up(s->byte_end, RLE_BLOCK) - s->block_first;
     TRY(alloc_native(s->data, s->byte_end - base));
     TRY(s->block_start.alloc((s->nblocks + 1) * sizeof(u64), true));
-    LAUNCH("enc_emit", k_enc_emit<false>, div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
-      s->lasthead.as<const u64>() - s->seg_first, s->head_carry, s->seg_base.as<const u64>() - s->seg_first, s->data.as<u8>() - base,
-      s->block_start.as<u64>() - s->block_first, (u32*)nullptr, (u64)0);
+    if(with_cum && s->nblocks > 0)
+    {
+      // block_start and cum32 hold the slice's blocks only: both are indexed by the global block number through shifted pointers
+      TRY(s->cum32.alloc(5 * s->nblocks * sizeof(u32)));
+      LAUNCH("enc_emit", (k_enc_emit<true, true>), div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
+        s->lasthead.as<const u64>() - s->seg_first, s->head_carry, s->seg_base.as<const u64>() - s->seg_first, s->data.as<u8>() - base,
+        s->block_start.as<u64>() - s->block_first, s->cum32.as<u32>() - s->block_first, s->nblocks, s->pos_first(), s->halo_symbol, s->sup.as<const u64>());
+    }
+    else
+    {
+      LAUNCH("enc_emit", k_enc_emit<false>, div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
+        s->lasthead.as<const u64>() - s->seg_first, s->head_carry, s->seg_base.as<const u64>() - s->seg_first, s->data.as<u8>() - base,
+        s->block_start.as<u64>() - s->block_first, (u32*)nullptr, (u64)0, (u64)0, 0u, (const u64*)nullptr);
+    }
   }
   else
   {
     s->block_first = div_up(byte_offset, RLE_BLOCK); s->nblocks = 0;
     TRY(s->block_start.alloc(sizeof(u64), true));
   }
+  s->bytes_high = std::max(s->bytes_high, s->device_bytes());
   s->table.release(); s->group_table.release(); s->group_base.release(); s->seg_base.release(); s->lasthead.release();
   return BWTM_OK;
+}
+} // namespace
+
+extern "C" int bwtm_slice_encode(bwtm_slice* s, uint64_t byte_offset)
+{
+  if(!s) { return fail(BWTM_EINVAL, "bwtm_slice_encode: null argument"); }
+  ENTER(s->ctx);
+  return slice_encode(s, byte_offset, false);
 }
 
 extern "C" uint64_t bwtm_slice_byte_first(const bwtm_slice* s)  { return s ? s->byte_first : 0; }

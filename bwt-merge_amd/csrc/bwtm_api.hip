@@ -8,6 +8,7 @@
     api/search.hip.h    rank array: frontier search / per-chain walk, finalize, downloads
     api/merge.hip.h     interleave, whole-path entry points (device-resident, consuming, host-to-host)
     api/slices.hip.h    output-range-sharded interleave + encode (one slice per GPU)
+    api/stream.hip.h    host-to-host merge whose second half runs slice by slice on one GPU, the result handed to the caller in pieces
     api/group.hip.h     the parts of a multi-GPU merge: shared control block (barrier, small all-gathers), exported arenas (raw pointer / HIP IPC)
     api/pmerge.hip.h    the merge over PARTITIONED records, one part per GPU: windows from byte shares, cuts, the routed search, the second half
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
@@ -38,6 +39,7 @@ using namespace bwtm;
 #include "api/search.hip.h"
 #include "api/merge.hip.h"
 #include "api/slices.hip.h"
+#include "api/stream.hip.h"
 #include "api/group.hip.h"
 #include "api/pmerge.hip.h"
 #ifdef BWTM_EXPERIMENTAL

@@ -26,6 +26,7 @@
     k_enc_*            RunBuffer + Run::write, block starts of BWT::build
                                                                     utils.h:121-142, support.h:256-282, bwt.cpp:496
     k_fold_*           byte-offset carry of Run::write across segments (array.size() % 64, support.h:267)
+    k_piece_fields     the samples of one piece of a streamed merge, from the encoder's block starts and cum32 (kernels/stream.hip.h)
     k_rank_batch, k_inverse_select_batch, k_extract, k_find_batch
                        BWT::rank / inverse_select / extract, FMI::find  bwt.cpp:318-464, fmi.h:195-221
 */
@@ -88,6 +89,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/search_range.hip.h"
 #include "kernels/interleave.hip.h"
 #include "kernels/encoder.hip.h"
+#include "kernels/stream.hip.h"
 #include "kernels/ingest.hip.h"
 
 } // namespace bwtm

@@ -32,6 +32,8 @@ static void printUsage()
   std::cerr << "                (the buffer options have no effect on the device)" << std::endl;
   std::cerr << "  -B            With several GPUs: sequence blocks instead (replicated records, every GPU searches a block of the" << std::endl;
   std::cerr << "                increment's sequences, one reduce-scatter of the rank-array bitvector by output range)" << std::endl;
+  std::cerr << "  -z N          One GPU: stream the last merge's result to the host in slices of N records of 128 positions (a multiple of 512;" << std::endl;
+  std::cerr << "                0 = chosen by the library): the device never holds the whole encoded result, and -v uploads the result again" << std::endl;
 #ifdef BWTM_EXPERIMENTAL
   std::cerr << "  -S            With several GPUs: sliced search (replicated records, every GPU advances a contiguous slice of the" << std::endl;
   std::cerr << "                sorted frontier; experimental build only)" << std::endl;
@@ -126,9 +128,9 @@ int main(int argc, char** argv)
   std::vector<std::string> input_formats;
   while((c = getopt(argc, argv,
 #ifdef BWTM_EXPERIMENTAL
-    "b:m:r:s:t:d:v:i:o:g:BPS"
+    "b:m:r:s:t:d:v:i:o:g:z:BPS"
 #else
-    "b:m:r:s:t:d:v:i:o:g:BP"
+    "b:m:r:s:t:d:v:i:o:g:z:BP"
 #endif
     )) != -1)
   {
@@ -146,6 +148,7 @@ int main(int argc, char** argv)
         for(std::string token; std::getline(ss, token, ','); ) { devices.push_back(std::stoi(token)); }
       }
       break;
+    case 'z': parameters.streamed = true; parameters.slice_records = std::stoul(optarg); break;
     case 'B': multi_gpu_mode = MultiGPUMode::SequenceBlocks; break;
     case 'P': multi_gpu_mode = MultiGPUMode::Partitioned; break;      // the default, without the fall-back to sequence blocks
 #ifdef BWTM_EXPERIMENTAL

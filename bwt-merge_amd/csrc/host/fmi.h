@@ -24,6 +24,9 @@ void load(FMI& fmi, const std::string& filename, const std::string& format);
   device wants (it partitions the work itself).
   lazy_host (an addition): the merged FMI is left on the device and its host form is produced when
   something asks for it; the tool sets it for every merge but the last of a chain.
+  streamed (an addition): the host-to-host merge runs its second half slice by slice (bwtm_merge_host_streamed, slice_records records
+  per slice, 0 = the library chooses) and the pieces are assembled into the result's arrays here: the device never holds the whole
+  encoded stream, and no device index is kept with the result.
 */
 struct MergeParameters
 {
@@ -36,7 +39,7 @@ struct MergeParameters
 
   MergeParameters() :
     run_buffer_size(RUN_BUFFER_SIZE), thread_buffer_size(THREAD_BUFFER_SIZE), merge_buffers(MERGE_BUFFERS),
-    threads(Parallel::max_threads), sequence_blocks(threads * BLOCKS_PER_THREAD), temp_dir("."), lazy_host(false) {}
+    threads(Parallel::max_threads), sequence_blocks(threads * BLOCKS_PER_THREAD), temp_dir("."), lazy_host(false), streamed(false), slice_records(0) {}
 
   void sanitize()
   {
@@ -67,6 +70,7 @@ struct MergeParameters
   size_type threads, sequence_blocks;
   std::string temp_dir;
   bool lazy_host;
+  bool streamed; size_type slice_records;
 };
 
 inline std::ostream& operator<<(std::ostream& out, const MergeParameters& p)
@@ -174,6 +178,74 @@ inline void* mergeSink(void* user, int what, uint64_t nbytes)
   return nullptr;
 }
 
+// The sink of bwtm_merge_host_streamed: the pieces' bytes are appended to the result's page-locked data, their fields kept per row at the
+// widest width seen so far (a narrower piece is widened on the way in, a wider one widens what is there) and laid out as
+// fields[6][blocks] / anchors[6][ceil(blocks / 64)] when the last piece has arrived.
+struct PieceAssembler
+{
+  BWT* bwt = nullptr;
+  int width = 1;
+  size_type blocks = 0, reserved = 0;                   // (the data array grows geometrically: a piece may be a few KB)
+  bool too_wide = false;                                // a piece in the full form: a block of 2^32 - 1 positions or more
+  std::vector<std::uint8_t> rows[BWT::SIGMA];
+  std::vector<uint64_t> anch[BWT::SIGMA];
+
+  static uint64_t get(const void* p, int w, size_type k)
+  {
+    return (w == 1 ? (uint64_t)((const std::uint8_t*)p)[k] : (w == 2 ? (uint64_t)((const std::uint16_t*)p)[k] : (uint64_t)((const std::uint32_t*)p)[k]));
+  }
+  static void put(std::uint8_t* p, int w, size_type k, uint64_t v)
+  {
+    if(w == 1) { p[k] = (std::uint8_t)v; } else if(w == 2) { ((std::uint16_t*)p)[k] = (std::uint16_t)v; } else { ((std::uint32_t*)p)[k] = (std::uint32_t)v; }
+  }
+  void widen(int to)
+  {
+    for(size_type c = 0; c < BWT::SIGMA; c++)
+    {
+      std::vector<std::uint8_t> wide(blocks * (size_type)to);
+      for(size_type k = 0; k < blocks; k++) { put(wide.data(), to, k, get(rows[c].data(), width, k)); }
+      rows[c].swap(wide);
+    }
+    width = to;
+  }
+  static int sink(void* user, const bwtm_piece* piece)
+  {
+    PieceAssembler& self = *(PieceAssembler*)user;
+    HostArray<byte_type>& bytes = self.bwt->data.bytes;
+    const size_type old = bytes.size();
+    if(piece->nbytes > 0)
+    {
+      if(old + piece->nbytes > self.reserved) { self.reserved = std::max<size_type>(old + piece->nbytes, 2 * self.reserved); bytes.reserve(self.reserved); }
+      bytes.resizeUninitialized(old + piece->nbytes);
+      std::memcpy(bytes.data() + old, piece->data, piece->nbytes);
+    }
+    const size_type ns = piece->sample_blocks;
+    if(ns == 0) { return 0; }
+    if(piece->sample_width == 8) { self.too_wide = true; return 1; }
+    if(piece->sample_width > self.width) { self.widen(piece->sample_width); }
+    for(size_type c = 0; c < BWT::SIGMA; c++)
+    {
+      self.rows[c].resize((self.blocks + ns) * (size_type)self.width);
+      for(size_type k = 0; k < ns; k++) { put(self.rows[c].data(), self.width, self.blocks + k, get(piece->fields, piece->sample_width, c * ns + k)); }
+      self.anch[c].insert(self.anch[c].end(), piece->anchors + c * piece->nanchors, piece->anchors + (c + 1) * piece->nanchors);
+    }
+    self.blocks += ns;
+    return 0;
+  }
+  void finish()
+  {
+    const size_type nanch = (blocks + 63) / 64, row_bytes = blocks * (size_type)width;
+    bwt->data.bytes.reserve(1);
+    bwt->anchors.resizeUninitialized(std::max<size_type>(BWT::SIGMA * nanch, 1)); bwt->anchors.resizeUninitialized(BWT::SIGMA * nanch);
+    bwt->fields.resizeUninitialized(std::max<size_type>((BWT::SIGMA * row_bytes + 1) / 2, 1)); bwt->fields.resizeUninitialized((BWT::SIGMA * row_bytes + 1) / 2);
+    for(size_type c = 0; c < BWT::SIGMA; c++)
+    {
+      if(row_bytes > 0) { std::memcpy((std::uint8_t*)bwt->fields.data() + c * row_bytes, rows[c].data(), row_bytes); }
+      std::copy(anch[c].begin(), anch[c].end(), bwt->anchors.begin() + c * nanch);
+    }
+  }
+};
+
 inline FMI::FMI(FMI& a, FMI& b, MergeParameters parameters)
 {
   if(a.alpha != b.alpha)
@@ -212,6 +284,43 @@ inline FMI::FMI(FMI& a, FMI& b, MergeParameters parameters)
 #ifdef VERBOSE_STATUS_INFO
     gpuCheck(bwtm_synchronize(), "FMI::FMI()");
     std::cerr << "bwt_merge: BWTs merged in " << (readTimer() - verbose_mid) << " seconds (the result stays on the device)" << std::endl;
+#endif
+  }
+  else if(parameters.streamed)
+  {
+    // Host to host with the second half in slices (bwtm_merge_host_streamed): the pieces are assembled into this object's arrays.
+    std::vector<uint64_t> cb(b.alpha.C.begin(), b.alpha.C.end()), ca(a.alpha.C.begin(), a.alpha.C.end());
+    const BlockArray& bdata = b.bwt.hostData();
+    bwtm_host_input hb = { bdata.data(), bdata.size(), b.sequences(), b.size(), cb.data() };
+    b.bwt.dropDevice();                                   // an announced upload of b is not used by this form
+    bwtm_host_output out;
+    bwtm_stream_stats stats;
+    PieceAssembler pieces; pieces.bwt = &this->bwt;
+    this->bwt.data.bytes.resizeUninitialized(0);
+    int rc = BWTM_OK;
+    if(a.bwt.deviceResident())
+    {
+      rc = bwtm_merge_host_streamed(a.bwt.releaseDevice(), nullptr, &hb, parameters.slice_records, BWTM_SAMPLES_COMPACT, PieceAssembler::sink, &pieces, &out, &stats);
+    }
+    else
+    {
+      const BlockArray& adata = a.bwt.hostData();
+      bwtm_host_input ha = { adata.data(), adata.size(), a.sequences(), a.size(), ca.data() };
+      rc = bwtm_merge_host_streamed(nullptr, &ha, &hb, parameters.slice_records, BWTM_SAMPLES_COMPACT, PieceAssembler::sink, &pieces, &out, &stats);
+    }
+    if(pieces.too_wide)
+    {
+      std::cerr << "FMI::FMI(): a block of the result encodes 2^32 - 1 positions or more; merge without MergeParameters::streamed" << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    gpuCheck(rc, "FMI::FMI()");
+    pieces.finish();
+    this->bwt.adoptHost(nullptr, out.blocks, pieces.width);
+    a.bwt.clear(); b.bwt.clear();
+#ifdef VERBOSE_STATUS_INFO
+    std::cerr << "bwt_merge: RA built in " << (stats.ms_upload + stats.ms_search) / 1000.0 << " seconds" << std::endl;
+    std::cerr << "bwt_merge: BWTs merged in " << stats.ms_second_half / 1000.0 << " seconds (" << stats.pieces << " pieces, slices of " << stats.slice_records
+              << " records, at most " << stats.slice_bytes_peak << " bytes of slices on the device)" << std::endl;
 #endif
   }
   else

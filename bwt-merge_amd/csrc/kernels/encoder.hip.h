@@ -431,13 +431,34 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_cum_expand(const u64* sup, co
   cum[0 * stride + b] = p - sum;
 }
 
-// The launch covers the segments [seg_first, seg_end): the pipelined download copies the bytes of one range to the
-// host while the next range is written.  CUM: also the samples' cumulative counts at every block start, in the compact form cum32 (above);
-// whole-index launches only (`recs` is then the index's own record array).
-template<bool CUM>
-__global__ void __launch_bounds__(BLOCK_THREADS, 4) k_enc_emit(const uint4* recs, u64 nrecs, u64 n, u64 ntiles, u64 seg_first, u64 seg_end,
-  const u64* prevhead, u64 head_carry, const u64* seg_base, u8* out, u64* block_start, u32* cum32, u64 cum_stride)
+// cum32 of a block that starts at p BEFORE the records an output-range slice holds (the block was opened by the run that is still open where
+// the slice starts, possibly slices earlier): the counts at the slice start -- the header of the slice's first record, relative to the
+// super block of the slice start -- minus the part of that run between p and the slice start (its symbol is the one before the slice),
+// re-based with the two super rows when p lies in an earlier super block.  No record before the slice is read.
+__device__ inline void slice_cum32_before(const uint4* recs, const u64* sup, u64 slice_start, u32 run_symbol, u64 p, u32 r[6])
 {
+  block_cum32_query(recs, slice_start, r);
+  const u64 s0 = slice_start >> SUPER_SHIFT, sp = p >> SUPER_SHIFT;
+  const u64 d = slice_start - p;
+#pragma unroll
+  for(u32 c = 1; c < 6; c++)
+  {
+    u64 v = (u64)r[c] - (run_symbol == c ? d : 0ull);
+    if(s0 != sp) { v += sup[s0 * SUP_STRIDE + c] - sup[sp * SUP_STRIDE + c]; }
+    r[c] = (u32)v;
+  }
+}
+
+// The launch covers the segments [seg_first, seg_end): the pipelined download copies the bytes of one range to the
+// host while the next range is written.  CUM: also the samples' cumulative counts at every block start, in the compact form cum32 (above).
+// SLICE (with CUM): `recs` holds the records of an output-range slice only, from position slice_start on (and the one record before it);
+// halo_symbol is the symbol at slice_start - 1 and `sup` the super table of the whole result.  Without SLICE the three are not read.
+template<bool CUM, bool SLICE = false>
+__global__ void __launch_bounds__(BLOCK_THREADS, 4) k_enc_emit(const uint4* recs, u64 nrecs, u64 n, u64 ntiles, u64 seg_first, u64 seg_end,
+  const u64* prevhead, u64 head_carry, const u64* seg_base, u8* out, u64* block_start, u32* cum32, u64 cum_stride,
+  u64 slice_start, u32 halo_symbol, const u64* sup)
+{
+  static_assert(CUM || !SLICE, "the slice form only differs in how it answers cum32");
   static_assert(BLOCK_THREADS / WAVE * ENC_STAGE_STRIDE <= ENC_DUMP && ENC_STAGE_STRIDE >= 4096 + 32, "staging areas below the dump region");
   __shared__ __attribute__((aligned(16))) u8 lds_all[ENC_LDS_BYTES];   // the kernel's only LDS object: it starts at LDS address 0 (checked below)
   u64 seg = seg_first + (((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 6);
@@ -536,7 +557,11 @@ __global__ void __launch_bounds__(BLOCK_THREADS, 4) k_enc_emit(const uint4* recs
     {
       const u64 tb0 = T << 6;
       u32 r[6];
-      if((p >> SUPER_SHIFT) != seg_super) { block_cum32_query(recs, p, r); }       // the run began in an earlier super block: one rank query
+      if((p >> SUPER_SHIFT) != seg_super)                                          // the run began in an earlier super block: one rank query
+      {
+        if(SLICE && p < slice_start) { slice_cum32_before(recs, sup, slice_start, halo_symbol, p, r); }   // ... not on records the slice does not hold
+        else { block_cum32_query(recs, p, r); }
+      }
       else
       {
         u32 n1, n2, n3, n4, n5; tile_counts(ti.p0, ti.p1, ti.p2, (bit == 0 ? 0ull : (~0ull >> (64 - bit))), n1, n2, n3, n4, n5);

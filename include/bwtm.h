@@ -316,6 +316,52 @@ int bwtm_slice_download_samples(bwtm_slice* slice, uint64_t next_block_start, ui
 /* Plain symbols of positions inside the slice. */
 int bwtm_slice_extract(bwtm_slice* slice, uint64_t first, uint64_t count, uint8_t* out);
 
+/* --- the streamed merge: the slices above, one after the other on ONE GPU ------------------------------------------
+
+   bwtm_merge_host() interleaves and encodes the whole result before it lets go of anything.  The streamed form uploads and searches in
+   the same way, then runs the second half slice by slice (interleave_range, last head, size table, encode) and hands every slice's
+   bytes and samples to the caller's SINK as soon as they are on the host: at most two slices are alive on the device, so the second
+   half needs records + bitvector + 2 slices instead of records + the whole stream (mergeBWT frees what it has consumed,
+   BlockArray::clearUntil, bwt.cpp:224-225).
+
+   A PIECE carries the bytes [byte_first, byte_first + nbytes) of BWT::data and the samples of the blocks whose END is known with it:
+   a block's length is known with the next block start, so piece g delivers the last block of the nearest earlier piece that had one and
+   all its own blocks but the last; the final piece (last != 0, always delivered, possibly empty) closes the last block.  A slice that
+   lies inside one run yields no piece.  The pointers are library-owned page-locked staging, valid until the sink returns.
+   sample_width: 0 = no samples were asked for; 1 / 2 / 4 = fields[6][sample_blocks] of that many bytes and anchors[6][nanchors], the
+   anchors of the global groups anchor_first .. anchor_first + nanchors - 1 (group k = blocks 64 k ..; those with 64 k inside the sample
+   range), the narrowest width that holds the piece's longest block (bwtm_index_samples_width's rule, per piece); 8 = block_end
+   [sample_blocks] and cum[6][sample_blocks] (always with BWTM_SAMPLES_FULL; in compact mode only when a block reaches 2^32 - 1
+   positions).  Laid end to end and widened to the largest width, the pieces' arrays are what bwtm_index_download_samples_compact /
+   bwtm_index_download_samples give for the whole result (the latter's column behind the last block is C: cum[c][blocks] = C[c + 1] - C[c]).
+   A sink that returns non-zero stops the merge: the call returns BWTM_EINVAL. */
+typedef struct
+{
+  uint64_t byte_first, nbytes; const uint8_t* data;
+  uint64_t sample_block_first, sample_blocks;
+  int sample_width;
+  const void* fields; const uint64_t* anchors;
+  uint64_t anchor_first, nanchors;
+  const uint64_t* block_end; const uint64_t* cum;
+  int last;
+} bwtm_piece;
+typedef int (*bwtm_piece_fn)(void* user, const bwtm_piece* piece);
+typedef struct
+{
+  uint64_t pieces;                           /* sink calls */
+  uint64_t slice_records;                    /* records per slice the call ran with */
+  uint64_t slice_bytes_peak;                 /* largest sum of the device buffers of the live slices and the call's device staging */
+  double ms_upload, ms_search, ms_second_half, ms_total;
+} bwtm_stream_stats;
+/* Exactly one of a_device (a kept device index, consumed also on failure) and a_host.  slice_records: a multiple of 512, or 0 = the library
+   chooses (two slices within a fixed share of the free device memory); at least the result's records = one slice.  want_samples:
+   BWTM_SAMPLES_NONE / _FULL / _COMPACT.  `out` receives the header fields, C, nbytes, blocks and the timings; its pointers stay NULL.
+   `stats` may be NULL.  The sink is called on the calling thread, between the library's own calls: it must not call the library on the
+   same context. */
+int bwtm_merge_host_streamed(bwtm_index* a_device, const bwtm_host_input* a_host, const bwtm_host_input* b_host,
+                             uint64_t slice_records, int want_samples, bwtm_piece_fn sink, void* user,
+                             bwtm_host_output* out, bwtm_stream_stats* stats);
+
 /* --- the merge over PARTITIONED records: one part per GPU, nothing replicated ---------------------------------
    (the thread fan-out of fmi.cpp:351-358 and utils.cpp:189-218 as ranges of the merged ORDER instead of blocks of
    b's sequences.)  A cut is a pair (cut_a[g], cut_b[g]) = (suffixes of a below w_g, suffixes of b below w_g) for a k-mer w_g; part g owns
