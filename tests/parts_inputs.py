@@ -1,5 +1,5 @@
-"""Inputs of the merge over partitioned records shared by tests/test_gpu_parts.py (parts as threads) and tests/test_gpu_parts_processes.py
-(parts as processes).  Texts are the oracle's: symbols 1..5, each sequence followed by a 0 ("$")."""
+"""Inputs and helpers of the merge over partitioned records shared by tests/test_gpu_parts.py (parts as threads), tests/test_gpu_parts_processes.py
+(parts as processes) and tests/test_gpu_second_half_forms.py.  Texts are the oracle's: symbols 1..5, each sequence followed by a 0 ("$")."""
 import numpy as np
 
 ODD_CASES = ["short", "one_base", "with_n", "tiny_b", "unequal", "empty_b"]
@@ -46,6 +46,27 @@ def wide_inputs(oracle):
     b = oracle.FMI.from_runs(small_b.symbols.astype(np.uint64), np.full(small_b.symbols.size, 2000, dtype=np.uint64))
     assert a.bases > (1 << 32)
     return a, b
+
+
+def host(gpu, x):
+    return gpu.host_index(x.data, x.samples[1], x.sequences, x.bases)
+
+
+def merge_parts(gpu, a, b, parts, kmer=0):
+    """-> (data, block_end, cum, stats, cuts): the parts' bytes and samples laid end to end."""
+    from bwt_merge_amd import partitioned
+    out = partitioned.merge_parts(gpu, host(gpu, a), host(gpu, b), parts, kmer=kmer, collect=lambda g, s: partitioned.slice_arrays(s))
+    try:
+        got = out["collected"]
+        total = out["slices"][0].total_nbytes
+        assert all(s.total_nbytes == total for s in out["slices"])
+        offsets = [s.byte_offset for s in out["slices"]]
+        assert offsets == sorted(offsets) and offsets[0] == 0
+        data = np.concatenate([g[0] for g in got]); be = np.concatenate([g[1] for g in got]); cum = np.concatenate([g[2] for g in got], axis=1)
+        assert data.size == total
+        return data, be, cum, out["stats"], out["cuts"]
+    finally:
+        out["release"]()
 
 
 def check_against_oracle(oracle, a, b, data, be, cum, threads=2):

@@ -11,6 +11,8 @@ import threading
 import numpy as np
 import pytest
 
+from second_half_inputs import repeated_collection
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,13 +24,6 @@ def gpu(bwtm):
     for k in ("search_algo", "frontier_epoch", "emit_budget", "l1_cap", "eager_cum_budget", "upload_chunk", "download_chunk"):
         bwtm.tune(k, 0)
     bwtm.trim()
-
-
-def repeated_collection(oracle, seed, nreads, readlen, copies):
-    """Oracle FMI of the collection (read 0 x copies, read 1 x copies, ...)."""
-    small = oracle.FMI.from_text(oracle.generate_reads(seed, nreads, readlen))
-    sym = small.symbols.astype(np.uint64)
-    return oracle.FMI.from_runs(sym, np.full(sym.size, copies, dtype=np.uint64))
 
 
 def upload(gpu, f):

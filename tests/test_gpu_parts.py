@@ -6,7 +6,8 @@ stream, bit for bit; no part ever holds a whole index or the whole bitvector."""
 import numpy as np
 import pytest
 
-from parts_inputs import ODD_CASES, check_against_oracle, odd_collection, truly_empty, wide_inputs
+from parts_inputs import ODD_CASES, check_against_oracle, host, merge_parts, odd_collection, truly_empty, wide_inputs
+from second_half_inputs import repetitive_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -17,27 +18,6 @@ def gpu(bwtm):
     yield bwtm
     bwtm.make_default_current()
     bwtm.trim()
-
-
-def host(gpu, x):
-    return gpu.host_index(x.data, x.samples[1], x.sequences, x.bases)
-
-
-def merge_parts(gpu, a, b, parts, kmer=0):
-    """-> (data, block_end, cum, stats, cuts): the parts' bytes and samples laid end to end."""
-    from bwt_merge_amd import partitioned
-    out = partitioned.merge_parts(gpu, host(gpu, a), host(gpu, b), parts, kmer=kmer, collect=lambda g, s: partitioned.slice_arrays(s))
-    try:
-        got = out["collected"]
-        total = out["slices"][0].total_nbytes
-        assert all(s.total_nbytes == total for s in out["slices"])
-        offsets = [s.byte_offset for s in out["slices"]]
-        assert offsets == sorted(offsets) and offsets[0] == 0
-        data = np.concatenate([g[0] for g in got]); be = np.concatenate([g[1] for g in got]); cum = np.concatenate([g[2] for g in got], axis=1)
-        assert data.size == total
-        return data, be, cum, out["stats"], out["cuts"]
-    finally:
-        out["release"]()
 
 
 @pytest.mark.parametrize("parts,kmer,range_ratio", [(1, 2, 8), (2, 1, 8), (3, 3, 0), (4, 4, 8), (8, 4, 8), (16, 3, 8), (2, 0, 0), (5, 4, 3), (4, 2, 1)])
@@ -98,16 +78,6 @@ def test_parts_wide_coordinates(gpu, oracle, rr):
     mbe, mcum = M.samples()
     assert np.array_equal(be, mbe) and np.array_equal(cum, mcum[:, :-1])
     M.free(); A.free(); B.free()
-
-
-def repetitive_reads(seed, genome_len, nreads, readlen):
-    rng = np.random.default_rng(seed)
-    genome = rng.integers(1, 5, genome_len, dtype=np.uint8)
-    starts = rng.integers(0, genome_len - readlen, nreads)
-    out = np.zeros((nreads, readlen + 1), dtype=np.uint8)
-    for k, s in enumerate(starts):
-        out[k, :readlen] = genome[s: s + readlen]
-    return out.reshape(-1)
 
 
 @pytest.mark.parametrize("glen,coverage", [(300000, 2), (200000, 4), (6000, 60)])

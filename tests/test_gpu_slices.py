@@ -68,22 +68,20 @@ def test_sliced_merge_of_read_sets(gpu, oracle, parts):
     ra.free()
 
 
-@pytest.mark.parametrize("parts", [1, 2, 3, 5, 8])
-def test_range_finalize_after_a_reduce_scatter(gpu, oracle, parts):
-    """The exchange the merge runs on several GPUs: every part owns an EQUAL range of the output and a bitvector that is complete only
-    inside it (what a reduce-scatter leaves: here a caller-owned copy of the full bitvector with every byte outside the range
-    overwritten).  bwtm_ra_range_counts of every part -> the small exchange (dist.combine_range_counts' arithmetic) ->
-    bwtm_ra_finalize_range -> bwtm_interleave_range; the slices' bytes and samples equal the oracle's merge.  Large enough for
-    several segments per part."""
+def check_range_finalize(gpu, oracle, a, b, A, B, parts, m=None, full_bits=None):
+    """The exchange the merge runs on several GPUs, for the oracle FMIs a and b and their uploads A and B: every part owns an EQUAL range
+    of the output and a bitvector that is complete only inside it (what a reduce-scatter leaves: here a caller-owned copy of the full
+    bitvector with every byte outside the range overwritten).  bwtm_ra_range_counts of every part -> the small exchange
+    (dist.combine_range_counts' arithmetic) -> bwtm_ra_finalize_range -> bwtm_interleave_range; the slices' bytes and samples equal the
+    oracle's merge.  m: the oracle's merge when the caller has it (a and b are consumed otherwise); full_bits: the words of the
+    finalized bitvector of a search the caller has made already.  A and B stay the caller's."""
     import torch
     from bwt_merge_amd.dist import fold_offsets, super_owners
-    ta = oracle.generate_reads(9101, 9000, 100); tb = oracle.generate_reads(9102, 7000, 100)
-    a, b = oracle.FMI.from_text(ta), oracle.FMI.from_text(tb)
-    A = gpu.Index.upload(a.data, a.sequences, a.bases); B = gpu.Index.upload(b.data, b.sequences, b.bases)
-    whole = gpu.RankArray(A, B)
-    whole.search(A, B, 0, b.sequences - 1)
-    full_bits = whole.finalize().bits()                                  # n_out bits as 64-bit words
-    whole.free()
+    if full_bits is None:
+        whole = gpu.RankArray(A, B)
+        whole.search(A, B, 0, b.sequences - 1)
+        full_bits = whole.finalize().bits()                              # n_out bits as 64-bit words
+        whole.free()
     nrecs = gpu.merged_records(A, B)
     bounds = [gpu.slice_bounds_equal(nrecs, parts, g) for g in range(parts)]
     shard_bytes = bounds[0][2]
@@ -123,7 +121,8 @@ def test_range_finalize_after_a_reduce_scatter(gpu, oracle, parts):
     offsets = fold_offsets(tables)
     for s, off in zip(slices, offsets):
         s.encode(off)
-    m, _ = oracle.merge(a, b, threads=2)
+    if m is None:
+        m, _ = oracle.merge(a, b, threads=2)
     assert np.array_equal(np.concatenate([s.data() for s in slices]), m.data)
     starts = [s.first_block_start() for s in slices]
     be, cum = [], []
@@ -133,8 +132,18 @@ def test_range_finalize_after_a_reduce_scatter(gpu, oracle, parts):
         be.append(x); cum.append(y)
     obe, ocum = m.samples
     assert np.array_equal(np.concatenate(be), obe) and np.array_equal(np.concatenate(cum, axis=1), ocum[:, :-1])
-    for x in slices + ras + [A, B]:
+    for x in slices + ras:
         x.free()
+
+
+@pytest.mark.parametrize("parts", [1, 2, 3, 5, 8])
+def test_range_finalize_after_a_reduce_scatter(gpu, oracle, parts):
+    """check_range_finalize on read sets large enough for several segments per part."""
+    ta = oracle.generate_reads(9101, 9000, 100); tb = oracle.generate_reads(9102, 7000, 100)
+    a, b = oracle.FMI.from_text(ta), oracle.FMI.from_text(tb)
+    A = gpu.Index.upload(a.data, a.sequences, a.bases); B = gpu.Index.upload(b.data, b.sequences, b.bases)
+    check_range_finalize(gpu, oracle, a, b, A, B, parts)
+    A.free(); B.free()
 
 
 @pytest.mark.parametrize("case", ["long_runs", "one_run", "runs_on_cuts", "tiny"])
