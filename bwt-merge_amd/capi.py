@@ -48,6 +48,11 @@ class StreamStats(C.Structure):
                 ("ms_upload", C.c_double), ("ms_search", C.c_double), ("ms_second_half", C.c_double), ("ms_total", C.c_double)]
 
 
+class UploadStats(C.Structure):
+    """bwtm_upload_stats"""
+    _fields_ = [("chunks", u64), ("chunk_bytes", u64), ("staging_bytes_peak", u64), ("ms_total", C.c_double)]
+
+
 PIECE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Piece))
 
 
@@ -111,6 +116,7 @@ SYMBOLS = [
     ("bwtm_trim", C.c_int, []),
     ("bwtm_tune", C.c_int, [C.c_char_p, C.c_longlong]),
     ("bwtm_index_upload", C.c_int, [p_u8, u64, u64, u64, p_u64, C.POINTER(vp)]),
+    ("bwtm_index_upload_streamed", C.c_int, [p_u8, u64, u64, u64, p_u64, C.POINTER(vp), C.POINTER(UploadStats)]),
     ("bwtm_index_from_device", C.c_int, [vp, u64, u64, u64, p_u64, C.POINTER(vp)]),
     ("bwtm_index_from_device_borrowed", C.c_int, [vp, u64, u64, u64, p_u64, C.POINTER(vp)]),
     ("bwtm_index_from_symbols_device", C.c_int, [vp, u64, C.POINTER(vp)]),
@@ -610,6 +616,19 @@ class Index:
             C_array, cp = _u64(C_array)
         check(lib().bwtm_index_upload(dp, data.size, sequences, bases, cp, C.byref(out)))
         return Index(out)
+
+    @staticmethod
+    def upload_streamed(data, sequences, bases, C_array=None):
+        """bwtm_index_upload_streamed: the index (records and super table only) from chunks of the bytes, the stream never resident as a whole.
+        Returns (Index, UploadStats)."""
+        data, dp = _u8(data)
+        out = vp()
+        cp = None
+        if C_array is not None:
+            C_array, cp = _u64(C_array)
+        stats = UploadStats()
+        check(lib().bwtm_index_upload_streamed(dp, data.size, sequences, bases, cp, C.byref(out), C.byref(stats)))
+        return Index(out), stats
 
     @staticmethod
     def from_device(ptr, nbytes, sequences, bases, C_array=None, borrow=False):

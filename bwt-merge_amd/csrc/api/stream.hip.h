@@ -257,6 +257,23 @@ int merge_host_streamed_impl(bwtm_index* a_dev, const bwtm_host_input* a_host, c
   std::memset(out, 0, sizeof(*out));
   // Upload and transcode as merge_host_impl does (copy stream: b's chunks, then a's; b is decoded, validated and transcoded while a's bytes
   // are still on the link) -- but b's native bytes go as soon as b is transcoded, not after a.
+  if(g_tune.stream_upload)
+  {
+    // The chunked upload: b's chunks, then a's, through one ring; neither stream is ever resident as a whole.  One synchronisation for both.
+    ChunkedUpload up;
+    TRY(up.prepare(std::max<u64>(b_host->nbytes, a_host ? a_host->nbytes : 0)));
+    int rc = chunked_index(up, b_host->data, b_host->nbytes, b_host->sequences, b_host->bases, 8, &st.b);
+    if(rc == BWTM_OK && a_host) { rc = chunked_index(up, a_host->data, a_host->nbytes, a_host->sequences, a_host->bases, 16, &st.a); }
+    const int rj = up.join();                                        // also on failure: the caller's buffers are free again
+    TRY(rc); TRY(rj);
+    TRY(ChunkedUpload::validate(st.b, b_host->sequences, b_host->bases, b_host->C, 8));
+    if(a_host) { TRY(ChunkedUpload::validate(st.a, a_host->sequences, a_host->bases, a_host->C, 16)); }
+    if(st.a->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_streamed: the index lives in another context"); }
+    WHOLE_INDEX(st.a, "bwtm_merge_host_streamed");
+    TRY(bwtm_index_drop_native(st.a));
+    st.peak = std::max(st.peak, up.peak);
+  }
+  else
   {
     UploadEvents ev_a, ev_b;
     bwtm_index* b = new bwtm_index(); st.b = b;

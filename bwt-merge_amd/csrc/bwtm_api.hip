@@ -5,6 +5,7 @@
 
     api/context.hip.h   contexts (device, streams, memory pool), errors, launch macros, profiling, scans
     api/index.hip.h     device index: pipelined upload + transcode, canonical encoder + pipelined download, queries
+    api/upload_stream.hip.h  the chunked upload: records + super table from a ring of chunk buffers, the stream never resident as a whole
     api/search.hip.h    rank array: frontier search / per-chain walk, finalize, downloads
     api/merge.hip.h     interleave, whole-path entry points (device-resident, consuming, host-to-host)
     api/slices.hip.h    output-range-sharded interleave + encode (one slice per GPU)
@@ -38,6 +39,7 @@ using namespace bwtm;
 #include "api/index.hip.h"
 #include "api/search.hip.h"
 #include "api/merge.hip.h"
+#include "api/upload_stream.hip.h"
 #include "api/slices.hip.h"
 #include "api/stream.hip.h"
 #include "api/group.hip.h"

@@ -34,6 +34,8 @@ static void printUsage()
   std::cerr << "                increment's sequences, one reduce-scatter of the rank-array bitvector by output range)" << std::endl;
   std::cerr << "  -z N          One GPU: stream the last merge's result to the host in slices of N records of 128 positions (a multiple of 512;" << std::endl;
   std::cerr << "                0 = chosen by the library): the device never holds the whole encoded result, and -v uploads the result again" << std::endl;
+  std::cerr << "  -u            With -z: upload that merge's host inputs in chunks as well (records are built chunk by chunk; no input's native" << std::endl;
+  std::cerr << "                stream is ever resident on the device as a whole).  The file written is the same" << std::endl;
 #ifdef BWTM_EXPERIMENTAL
   std::cerr << "  -S            With several GPUs: sliced search (replicated records, every GPU advances a contiguous slice of the" << std::endl;
   std::cerr << "                sorted frontier; experimental build only)" << std::endl;
@@ -128,9 +130,9 @@ int main(int argc, char** argv)
   std::vector<std::string> input_formats;
   while((c = getopt(argc, argv,
 #ifdef BWTM_EXPERIMENTAL
-    "b:m:r:s:t:d:v:i:o:g:z:BPS"
+    "b:m:r:s:t:d:v:i:o:g:z:uBPS"
 #else
-    "b:m:r:s:t:d:v:i:o:g:z:BP"
+    "b:m:r:s:t:d:v:i:o:g:z:uBP"
 #endif
     )) != -1)
   {
@@ -149,6 +151,7 @@ int main(int argc, char** argv)
       }
       break;
     case 'z': parameters.streamed = true; parameters.slice_records = std::stoul(optarg); break;
+    case 'u': parameters.stream_upload = true; break;
     case 'B': multi_gpu_mode = MultiGPUMode::SequenceBlocks; break;
     case 'P': multi_gpu_mode = MultiGPUMode::Partitioned; break;      // the default, without the fall-back to sequence blocks
 #ifdef BWTM_EXPERIMENTAL
@@ -173,6 +176,7 @@ int main(int argc, char** argv)
     }
   }
 
+  if(parameters.stream_upload && !parameters.streamed) { std::cerr << "bwt_merge: -u is valid only with -z" << std::endl; std::exit(EXIT_FAILURE); }
   int inputs = (argc - 1) - optind;
   if(inputs < 2) { std::cerr << "bwt_merge: Output file not specified" << std::endl; std::exit(EXIT_FAILURE); }
   if(input_formats.empty()) { input_formats.assign(inputs, NativeFormat::tag()); }

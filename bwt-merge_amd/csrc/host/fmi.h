@@ -27,6 +27,8 @@ void load(FMI& fmi, const std::string& filename, const std::string& format);
   streamed (an addition): the host-to-host merge runs its second half slice by slice (bwtm_merge_host_streamed, slice_records records
   per slice, 0 = the library chooses) and the pieces are assembled into the result's arrays here: the device never holds the whole
   encoded stream, and no device index is kept with the result.
+  stream_upload (with streamed): the host inputs of that merge go through the chunked upload (bwtm_tune "stream_upload"): neither
+  input's native stream is ever resident on the device as a whole.
 */
 struct MergeParameters
 {
@@ -39,7 +41,7 @@ struct MergeParameters
 
   MergeParameters() :
     run_buffer_size(RUN_BUFFER_SIZE), thread_buffer_size(THREAD_BUFFER_SIZE), merge_buffers(MERGE_BUFFERS),
-    threads(Parallel::max_threads), sequence_blocks(threads * BLOCKS_PER_THREAD), temp_dir("."), lazy_host(false), streamed(false), slice_records(0) {}
+    threads(Parallel::max_threads), sequence_blocks(threads * BLOCKS_PER_THREAD), temp_dir("."), lazy_host(false), streamed(false), slice_records(0), stream_upload(false) {}
 
   void sanitize()
   {
@@ -71,6 +73,7 @@ struct MergeParameters
   std::string temp_dir;
   bool lazy_host;
   bool streamed; size_type slice_records;
+  bool stream_upload;
 };
 
 inline std::ostream& operator<<(std::ostream& out, const MergeParameters& p)
@@ -298,6 +301,7 @@ inline FMI::FMI(FMI& a, FMI& b, MergeParameters parameters)
     PieceAssembler pieces; pieces.bwt = &this->bwt;
     this->bwt.data.bytes.resizeUninitialized(0);
     int rc = BWTM_OK;
+    gpuCheck(bwtm_tune("stream_upload", parameters.stream_upload ? 1 : 0), "FMI::FMI()");
     if(a.bwt.deviceResident())
     {
       rc = bwtm_merge_host_streamed(a.bwt.releaseDevice(), nullptr, &hb, parameters.slice_records, BWTM_SAMPLES_COMPACT, PieceAssembler::sink, &pieces, &out, &stats);

@@ -246,12 +246,31 @@ __device__ inline u64 group_block_start(const u64* blen, u64 nblocks, u64 first,
 
 // Super table from the native stream: one wave per super.  The counts at position p are the counts at
 // the start of p's group plus the runs of the group's blocks before p (one lane per block).
-__global__ void __launch_bounds__(BLOCK_THREADS) k_build_sup(const u8* data, u64 nbytes, const u64* blen,
-  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, u64* sup, u64 nsup)
+// run_decode that reads no byte at or behind `end`: false (and nothing decoded) for a run whose bytes are cut off there, which k_block_len does not
+// count either.  For bytes that have not been validated: a stretch of continuation bytes must not lead the decoder out of the buffer.
+__device__ inline bool run_decode_within(const u8* data, u64& pos, u64 end, u32& sym, u64& len)
+{
+  const u32 code = data[pos]; pos++;
+  sym = code % 6; len = code / 6 + 1;
+  if(len >= MAX_RUN)
+  {
+    u32 shift = 0, v;
+    do
+    {
+      if(pos >= end) { return false; }
+      v = data[pos]; pos++; len += (u64)(v & 0x7F) << (shift & 63u); shift += 7;
+    } while(v & 0x80);
+  }
+  return true;
+}
+
+// Row s of the super table, by one wave (s < nsup; p = s << SUPER_SHIFT lies inside the position range of the group tables, or p >= n).
+// BOUNDED: the decoder stays inside the lane's block (the chunked upload, whose bytes are not validated yet).
+template<bool BOUNDED>
+__device__ inline void build_sup_row(const u8* data, u64 nbytes, const u64* blen,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, u64* sup, u64 s)
 {
   const u32 lane = lane_id();
-  const u64 s = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 6;
-  if(s >= nsup) { return; }
   const u64 p = s << SUPER_SHIFT;
   u64 g = ngroups;                                  // column of the totals
   u64 c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
@@ -268,7 +287,9 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_build_sup(const u8* data, u64
       const u64 end = (nbytes - rle >= RLE_BLOCK ? rle + RLE_BLOCK : nbytes);
       while(rle < end && pos < p)
       {
-        u32 sym; u64 len; run_decode(data, rle, sym, len);
+        u32 sym; u64 len;
+        if(BOUNDED) { if(!run_decode_within(data, rle, end, sym, len)) { break; } }
+        else { run_decode(data, rle, sym, len); }
         u64 take = (p - pos < len ? p - pos : len);
         c1 += (sym == 1 ? take : 0); c2 += (sym == 2 ? take : 0); c3 += (sym == 3 ? take : 0);
         c4 += (sym == 4 ? take : 0); c5 += (sym == 5 ? take : 0);
@@ -284,6 +305,14 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_build_sup(const u8* data, u64
     out[1] = gcum[1 * gstride + g] + c1; out[2] = gcum[2 * gstride + g] + c2; out[3] = gcum[3 * gstride + g] + c3;
     out[4] = gcum[4 * gstride + g] + c4; out[5] = gcum[5 * gstride + g] + c5;
   }
+}
+
+__global__ void __launch_bounds__(BLOCK_THREADS) k_build_sup(const u8* data, u64 nbytes, const u64* blen,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, u64* sup, u64 nsup)
+{
+  const u64 s = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 6;
+  if(s >= nsup) { return; }
+  build_sup_row<false>(data, nbytes, blen, gcum, gstride, nblocks, ngroups, n, sup, s);
 }
 
 // Records from the native stream.  The wave of group g owns the records that START inside the group's
@@ -311,9 +340,12 @@ constexpr u32 BR_FILLS = 256;
 // walk that builds the record's twelve words in registers, one mask per run and word -- no atomics, no planes in LDS.  Bit-exact in all parity
 // tests, and slower everywhere: 13.0 vs 12.3 ms at 300 x, 12.9 vs 8.2 at 30 x, 8.0 vs 1.8 on iid reads (2 x 20 M): the walk is a loop of
 // dependent LDS reads whose trip count differs from lane to lane, at 2 waves per SIMD.  DESIGN_HISTORY.md, round 6.)
-template<u32 BR_WINDOW, int WAVES, bool FILL, bool UNIFORM = false>
-__global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64 nbytes, const u64* blen, u64* block_start,
-  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, const u64* sup, uint4* recs, u64 nrecs)
+// CHUNK (the chunked upload, k_build_recs_chunk below): data, blen and the group tables are those of ONE chunk of whole groups plus its two
+// lookahead blocks; only the stream's last chunk has a group that owns the rest; the block starts are not kept; and the record numbers are
+// clamped to the buffer, because the bytes have not been validated against the header yet.
+template<u32 BR_WINDOW, int WAVES, bool FILL, bool UNIFORM, bool CHUNK>
+__device__ __forceinline__ void build_recs_body(const u8* data, u64 nbytes, const u64* blen, u64* block_start,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, const u64* sup, uint4* recs, u64 nrecs, bool last_chunk)
 {
   constexpr u32 PW = BR_WINDOW / 32;                             // words per plane
   __shared__ u32 stage[WAVES][STAGE_ROWS * STAGE_WORDS];
@@ -324,17 +356,21 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
   const u64 g = (u64)blockIdx.x * WAVES + wave;
   if(g >= ngroups) { return; }
   const u64 first = g * GROUP;
-  const bool last_group = (g + 1 == ngroups);
+  const bool last_group = (g + 1 == ngroups) && (!CHUNK || last_chunk);
   const u32 nb = (nblocks > first ? (nblocks - first > (u64)STAGE_ROWS ? (u32)STAGE_ROWS : (u32)(nblocks - first)) : 0u);
   const u64* gpos = gcum + 6 * gstride;                          // start position of every group (gpos[ngroups] = n)
   const u64 S = gpos[g];
   // the starts of the wave's 64 blocks: written out for the group's own 62 (block_start: the set bits of block_boundaries, bwt.cpp:496, plus one)
   u64 blen_own;
   const u64 bstart_all = group_block_start(blen, nblocks, first, S, blen_own);
-  if(lane < (u32)GROUP && first + lane < nblocks) { block_start[first + lane] = bstart_all; }
-  if(last_group && lane == 0) { block_start[nblocks] = gpos[ngroups]; }
-  const u64 q_lo = (S + REC_POS - 1) >> REC_SHIFT;
-  const u64 q_hi = (last_group ? nrecs : (gpos[g + 1] + REC_POS - 1) >> REC_SHIFT);
+  if(!CHUNK)
+  {
+    if(lane < (u32)GROUP && first + lane < nblocks) { block_start[first + lane] = bstart_all; }
+    if(last_group && lane == 0) { block_start[nblocks] = gpos[ngroups]; }
+  }
+  u64 q_lo = (S + REC_POS - 1) >> REC_SHIFT;
+  u64 q_hi = (last_group ? nrecs : (gpos[g + 1] + REC_POS - 1) >> REC_SHIFT);
+  if(CHUNK) { q_lo = (q_lo < nrecs ? q_lo : nrecs); q_hi = (q_hi < nrecs ? q_hi : nrecs); }       // whatever the bytes say
   if(q_lo >= q_hi) { return; }                                  // wave-uniform: no record starts in this group
   u32* rows = stage[wave];
   if(nb > 0) { stage_blocks(data, nbytes, first, nb, rows); }
@@ -353,11 +389,14 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
     if(FILL && lane == 0) { fill_count[wave] = 0; }
     wave_sync_lds();
     const u64 we = (ws + BR_WINDOW < pos_end ? ws + BR_WINDOW : pos_end);
-    const bool inside = (have && bstart >= ws && bend <= ws + BR_WINDOW);
+    // (CHUNK: the same test in a form that a block length near 2^64 cannot wrap around)
+    const bool inside = (CHUNK ? (have && bstart >= ws && bstart - ws <= BR_WINDOW && bend - bstart <= BR_WINDOW - (bstart - ws))
+                               : (have && bstart >= ws && bend <= ws + BR_WINDOW));
     // Queues `nwords` whole words from `word` on for the cooperative fill; returns the number of words taken over
     // (0 if the queue is full: the caller then deposits them itself).
     auto queue_fill = [&](u32 sym, u32 word, u32 nwords) -> u32
     {
+      if(CHUNK && (word >= PW || nwords > PW - word)) { return 0; }      // unvalidated bytes: only words of the plane
       const u32 slot = atomicAdd(&fill_count[wave], 1u);
       if(slot >= BR_FILLS) { return 0; }
       fill_list[wave][slot] = word | ((nwords - 1) << 10) | (sym << 20);      // word < 1024, nwords <= 1024
@@ -402,7 +441,7 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
           fill = upto; len -= take;
           if(fill == 32u)
           {
-            atomicOr(&pl[wi], lo0); atomicOr(&pl[PW + wi], lo1); atomicOr(&pl[2 * PW + wi], lo2);       // edge words are shared with the neighbours
+            if(!CHUNK || wi < PW) { atomicOr(&pl[wi], lo0); atomicOr(&pl[PW + wi], lo1); atomicOr(&pl[2 * PW + wi], lo2); }   // edge words are shared with the neighbours
             lo0 = 0; lo1 = 0; lo2 = 0; fill = 0; wi++;
           }
           if(len >= 32u)
@@ -413,7 +452,8 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
             if(sym != 0)
             {
               const u32 done = (FILL && n >= 4 ? queue_fill(sym, wi, n) : 0u);
-              for(u32 j = done; j < n; j++) { pl[wi + j] = s0; pl[PW + wi + j] = s1; pl[2 * PW + wi + j] = s2; }
+              const u32 upto_w = (CHUNK ? (wi < PW ? (n < PW - wi ? n : PW - wi) : 0u) : n);           // (CHUNK: the lengths of a block's runs may contradict its length)
+              for(u32 j = done; j < upto_w; j++) { pl[wi + j] = s0; pl[PW + wi + j] = s1; pl[2 * PW + wi + j] = s2; }
             }
             wi += n;
           }
@@ -436,7 +476,7 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
       u32 fill = (u32)(bstart - ws) & 31u, wi = (u32)(bstart - ws) >> 5;
       auto flush = [&]()
       {
-        atomicOr(&pl[wi], lo0); atomicOr(&pl[PW + wi], lo1); atomicOr(&pl[2 * PW + wi], lo2);   // edge words are shared with the neighbours
+        if(!CHUNK || wi < PW) { atomicOr(&pl[wi], lo0); atomicOr(&pl[PW + wi], lo1); atomicOr(&pl[2 * PW + wi], lo2); }   // edge words are shared with the neighbours
         lo0 = hi0; lo1 = hi1; lo2 = hi2; hi0 = 0; hi1 = 0; hi2 = 0; fill -= 32; wi++;
       };
       auto append = [&](u32 sym, u32 take)                      // 1 <= take <= 32, fill < 32
@@ -642,6 +682,91 @@ __global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64
     }
     wave_sync_lds();                                             // the planes are cleared again by the next window
   }
+}
+
+template<u32 BR_WINDOW, int WAVES, bool FILL, bool UNIFORM = false>
+__global__ void __launch_bounds__(WAVES * WAVE) k_build_recs(const u8* data, u64 nbytes, const u64* blen, u64* block_start,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, const u64* sup, uint4* recs, u64 nrecs)
+{
+  build_recs_body<BR_WINDOW, WAVES, FILL, UNIFORM, false>(data, nbytes, blen, block_start, gcum, gstride, nblocks, ngroups, n, sup, recs, nrecs, true);
+}
+
+//------------------------------------------------------------------------------
+// The chunked upload (api/upload_stream.hip.h): the stream arrives in chunks of whole groups and is transcoded chunk by chunk, so that no more
+// than a ring of chunks is ever resident.  What one chunk hands to the next lives on the device, in the STATE buffer of UP_STATE_WORDS u64:
+//   [0, 6)  occurrences of every symbol before the next chunk      [6]  k_block_len's flags (its low 32 bits)
+//   [7]     position at which the next chunk starts                [8]  the sticky error word
+// so the chunks' kernels are ordered by the compute stream alone.  Per chunk: k_block_len over the chunk's own bytes (its groups and the group
+// of the two lookahead blocks, whose counts are not used), k_chunk_carry, k_build_sup_chunk, k_build_recs_chunk.
+// The header (bases) is validated against the stream only after the last chunk: until then the bytes are untrusted, every global store
+// is bounded by what the header allocated, and once the error word is set the kernels that write the index return at once.
+constexpr u32 UP_STATE_WORDS = 16;
+constexpr u32 UP_STATE_FLAGS = 6, UP_STATE_POS = 7, UP_STATE_ERROR = 8;
+constexpr u64 UP_ERR_BEYOND = 1, UP_ERR_SHORT_BLOCK = 2, UP_ERR_TOTAL = 4;
+
+// Exclusive scans of the chunk's seven group rows (gt[c * gstride + g], g < ngroups: k_block_len's counts) in place, plus what the state
+// carries; column `ngroups` of every row and the state receive the values at the end of the chunk.  One workgroup: a thread sums a
+// contiguous share of a row, the shares are scanned, the thread rewrites its share.
+// Error: the position passes `bases`, the last chunk does not end at `bases`, or k_block_len flagged a full block of fewer than 64 positions.
+// The totals go on counting after an error: the host reports them as the one-shot upload does.
+__global__ void __launch_bounds__(BLOCK_THREADS) k_chunk_carry(u64* gt, u64 gstride, u64 ngroups, u64* state, u64 bases, u32 last_chunk)
+{
+  __shared__ u64 wave_tot[BLOCK_THREADS / WAVE];
+  const u32 t = threadIdx.x, lane = lane_id(), wave = t >> 6;
+  const u64 share = (ngroups + BLOCK_THREADS - 1) / BLOCK_THREADS;
+  const u64 from = (t * share < ngroups ? t * share : ngroups), to = (from + share < ngroups ? from + share : ngroups);
+  u64 end_pos = 0;
+#pragma unroll 1
+  for(u32 c = 0; c < 7; c++)
+  {
+    u64* row = gt + (u64)c * gstride;
+    u64* carried_at = state + (c < 6 ? c : UP_STATE_POS);
+    const u64 carried = *carried_at;
+    u64 mine = 0;
+    for(u64 g = from; g < to; g++) { mine += row[g]; }
+    const u64 incl = wave_incl_sum(mine);
+    if(lane == WAVE - 1) { wave_tot[wave] = incl; }
+    __syncthreads();                                              // every thread has read the carried value
+    u64 before = carried, total = carried;
+#pragma unroll
+    for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { before += (w < wave ? wave_tot[w] : 0); total += wave_tot[w]; }
+    u64 run = before + incl - mine;
+    for(u64 g = from; g < to; g++) { const u64 v = row[g]; row[g] = run; run += v; }
+    if(t == 0) { row[ngroups] = total; *carried_at = total; }
+    end_pos = total;
+    __syncthreads();                                              // wave_tot is reused by the next row
+  }
+  if(t == 0)
+  {
+    u64 err = state[UP_STATE_ERROR];
+    if(end_pos > bases) { err |= UP_ERR_BEYOND; }
+    if(((u32)state[UP_STATE_FLAGS] & 1u) != 0) { err |= UP_ERR_SHORT_BLOCK; }
+    if(last_chunk != 0 && end_pos != bases) { err |= UP_ERR_TOTAL; }
+    state[UP_STATE_ERROR] = err;
+  }
+}
+
+// The rows of the supers whose position falls inside the chunk's position range [gpos[0], gpos[ngroups]) -- known on the device only, so the
+// launch covers all supers and every wave tests its own; the rows with p >= n (the totals) belong to the last chunk.
+__global__ void __launch_bounds__(BLOCK_THREADS) k_build_sup_chunk(const u8* data, u64 nbytes, const u64* blen,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, u64* sup, u64 nsup, const u64* state, u32 last_chunk)
+{
+  const u64 s = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 6;
+  if(s >= nsup || state[UP_STATE_ERROR] != 0) { return; }
+  const u64 p = s << SUPER_SHIFT;
+  const u64* gpos = gcum + 6 * gstride;
+  const bool mine = (p < n ? (p >= gpos[0] && p < gpos[ngroups]) : last_chunk != 0);       // wave-uniform
+  if(!mine) { return; }
+  build_sup_row<true>(data, nbytes, blen, gcum, gstride, nblocks, ngroups, n, sup, s);
+}
+
+// The records that start inside the chunk, at their absolute numbers in the whole index's buffer.
+template<u32 BR_WINDOW, int WAVES, bool FILL, bool UNIFORM = false>
+__global__ void __launch_bounds__(WAVES * WAVE) k_build_recs_chunk(const u8* data, u64 nbytes, const u64* blen,
+  const u64* gcum, u64 gstride, u64 nblocks, u64 ngroups, u64 n, const u64* sup, uint4* recs, u64 nrecs, const u64* state, u32 last_chunk)
+{
+  if(state[UP_STATE_ERROR] != 0) { return; }
+  build_recs_body<BR_WINDOW, WAVES, FILL, UNIFORM, true>(data, nbytes, blen, nullptr, gcum, gstride, nblocks, ngroups, n, sup, recs, nrecs, last_chunk != 0);
 }
 
 // cum[c * stride + b] = occurrences of c before the start of block first + b, b in [0, count)

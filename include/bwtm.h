@@ -87,6 +87,17 @@ int bwtm_index_upload(const uint8_t* data, uint64_t nbytes, uint64_t sequences, 
 /* The upload is chunked: the H2D copy of chunk k + 1 runs on the context's copy stream while the first
    decode pass of chunk k runs on its compute stream.  `C`, when given, must agree with the symbol
    counts of the stream (BWTM_EINVAL otherwise). */
+/* The same index without the stream ever being resident on the device as a whole: the bytes travel in chunks of the upload_chunk knob
+   (whole groups of 62 blocks) through a ring of at most three chunk buffers, and the records of chunk k are built while chunk k + 1 is on
+   the link; the running position and symbol counts stay on the device, and the header is validated once, after the last chunk, with
+   the verdicts of bwtm_index_upload (on failure the half-built index is freed).  The result holds records and super table only, like
+   the result of bwtm_interleave: bwtm_index_bytes() is 0 until bwtm_index_encode().
+   staging_bytes_peak: the largest sum of the device buffers the call held besides the records and the super table; it does not depend
+   on nbytes (at most 4 x chunk_bytes + 64 KiB).  chunk_bytes: the upload_chunk knob in whole groups, no more than the stream's groups.
+   `stats` may be NULL. */
+typedef struct { uint64_t chunks, chunk_bytes, staging_bytes_peak; double ms_total; } bwtm_upload_stats;
+int bwtm_index_upload_streamed(const uint8_t* data, uint64_t nbytes, uint64_t sequences, uint64_t bases,
+                               const uint64_t C[BWTM_SIGMA + 1], bwtm_index** out, bwtm_upload_stats* stats /* may be NULL */);
 /* Same, from a device buffer that already holds the native bytes (the bytes are copied). */
 int bwtm_index_from_device(const void* device_data, uint64_t nbytes, uint64_t sequences, uint64_t bases,
                            const uint64_t C[BWTM_SIGMA + 1], bwtm_index** out);
@@ -357,7 +368,9 @@ typedef struct
    chooses (two slices within a fixed share of the free device memory); at least the result's records = one slice.  want_samples:
    BWTM_SAMPLES_NONE / _FULL / _COMPACT.  `out` receives the header fields, C, nbytes, blocks and the timings; its pointers stay NULL.
    `stats` may be NULL.  The sink is called on the calling thread, between the library's own calls: it must not call the library on the
-   same context. */
+   same context.
+   bwtm_tune("stream_upload", 1): b and then a_host go through the chunked upload (bwtm_index_upload_streamed), so that neither input's
+   native stream is ever resident as a whole; ms_upload covers it, slice_bytes_peak counts its ring as well.  The pieces are the same. */
 int bwtm_merge_host_streamed(bwtm_index* a_device, const bwtm_host_input* a_host, const bwtm_host_input* b_host,
                              uint64_t slice_records, int want_samples, bwtm_piece_fn sink, void* user,
                              bwtm_host_output* out, bwtm_stream_stats* stats);
