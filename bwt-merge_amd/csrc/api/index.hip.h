@@ -81,8 +81,8 @@ int alloc_native(DevBuf& buf, u64 nbytes)
   return BWTM_OK;
 }
 
-// Step 1.  Three parts, so that a caller can queue the copies of several inputs before any decode pass (bwtm_merge_host):
-//   upload_prepare   allocates the sample arrays
+// Step 1.  Three parts, so that a caller can queue the copies of several inputs before any decode pass (upload_pipelined):
+//   upload_prepare   allocates the sample arrays (upload_index: a new index with its native buffer, prepared)
 //   upload_copies    (host sources only) copies the bytes into x->data in chunks on the copy stream, one event per chunk
 //   upload_decode    queues the first decode pass (k_block_len) chunk by chunk on the compute stream; the pass over chunk k waits
 //                    for chunk k's event only, so it runs while chunk k + 1 is in flight
@@ -118,7 +118,19 @@ int upload_prepare(bwtm_index* x)
   return BWTM_OK;
 }
 
-// The caller has forked the copy stream (fork_copy_stream: x->data may be a recycled block with queued users).
+// A new index of the current context, prepared for the upload of a host-resident stream.  *out belongs to the caller from the moment it
+// is set, also on failure: the caller's own cleanup path deletes it.
+int upload_index(const bwtm_host_input& in, bwtm_index** out)
+{
+  bwtm_index* x = new bwtm_index();
+  *out = x;
+  x->ctx = t_ctx; x->nbytes = in.nbytes; x->n = in.bases; x->m = in.sequences;
+  TRY(alloc_native(x->data, in.nbytes));
+  return upload_prepare(x);
+}
+
+// The caller has forked the copy stream (fork_copy_stream: x->data may be a recycled block with queued users).  An empty stream
+// queues no copy (its one event is recorded all the same), so host_src is never read then and may be anything.
 int upload_copies(bwtm_index* x, const u8* host_src, UploadEvents& events)
 {
   const u64 group_bytes = (u64)GROUP * RLE_BLOCK;
@@ -255,6 +267,69 @@ int upload_blocking(bwtm_index* x, const u8* host_src, u64 sequences, u64 bases,
   if(e1 != hipSuccess || e2 != hipSuccess) { return fail(BWTM_ENODEV, "upload failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
   TRY(upload_validate(x, sequences, bases, C, 0));
   TRY(transcode(x));
+  return BWTM_OK;
+}
+
+// Joins the copy stream and the compute stream -- nothing touches the caller's buffers after this -- and reports the first error as
+// "<what> failed".  A call that has failed already (rc) is joined all the same and keeps its own verdict.
+int join_streams(const char* what, int rc = BWTM_OK)
+{
+  hipError_t e1 = hipStreamSynchronize(CTX.copy_stream), e2 = hipStreamSynchronize(CTX.stream);
+  if(rc != BWTM_OK) { return rc; }
+  if(e1 != hipSuccess || e2 != hipSuccess) { return fail(BWTM_ENODEV, "%s failed: %s", what, hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
+  return BWTM_OK;
+}
+
+// One input of upload_pipelined: its header and bytes, where its index is, the events of its chunk copies.  The index is made here
+// (upload_index: *x is the caller's from then on, also on failure) unless the input is `queued`: then *x is prepared and its copies are
+// on the copy stream already (a pending bwtm_upload).  No host: the input is not there.
+struct UploadSlot
+{
+  const bwtm_host_input* host = nullptr;
+  bwtm_index** x = nullptr;
+  UploadEvents* events = nullptr;
+  bool queued = false;
+};
+
+// The upload of the two inputs of a host-to-host merge.  The copies of all inputs are queued first (copy stream: b's chunks, then a's,
+// then those of `next`, the announced input of the FOLLOWING merge, which travel under this merge's search).  b's decode pass and scans
+// run on the compute stream while b's later chunks arrive; the host then waits for b's scan results only -- a's bytes are still on the
+// link --, VALIDATES b's header against the stream and only then queues b's transcode, which sizes its output from the header (a wrong
+// `bases` or a non-canonical stream must never reach k_build_recs).  a follows the same way.  Without a.host the first input is on the
+// device already.  release_b_first: b's native bytes go as soon as b is transcoded (otherwise the caller releases them, after a).
+// The caller joins the streams when the call fails.
+int upload_pipelined(const UploadSlot& a, const UploadSlot& b, const UploadSlot& next, bool release_b_first)
+{
+  if(!b.queued) { TRY(upload_index(*b.host, b.x)); }
+  if(next.host) { TRY(upload_index(*next.host, next.x)); }
+  if(a.host) { TRY(upload_index(*a.host, a.x)); }
+  TRY(fork_copy_stream());                                        // recycled blocks may have queued users on the compute stream
+  if(!b.queued) { TRY(upload_copies(*b.x, b.host->data, *b.events)); }
+  if(a.host) { TRY(upload_copies(*a.x, a.host->data, *a.events)); }
+  if(next.host) { TRY(upload_copies(*next.x, next.host->data, *next.events)); }
+  TRY(upload_decode(*b.x, b.events));
+  TRY(upload_scan(*b.x, 8));
+  hipEvent_t b_scanned = nullptr;
+  HIP_TRY(hipEventCreateWithFlags(&b_scanned, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(b_scanned, CTX.stream);
+  if(e == hipSuccess) { e = hipEventSynchronize(b_scanned); }
+  (void)hipEventDestroy(b_scanned);
+  if(e != hipSuccess) { return fail(BWTM_ENODEV, "upload failed: %s", hipGetErrorString(e)); }
+  TRY(upload_validate(*b.x, b.host->sequences, b.host->bases, b.host->C, 8));
+  TRY(transcode(*b.x));
+  if(release_b_first) { TRY(bwtm_index_drop_native(*b.x)); }
+  if(a.host)
+  {
+    TRY(upload_decode(*a.x, a.events));
+    TRY(upload_scan(*a.x, 16));
+  }
+  // (the compute stream has waited for every chunk of a and b; the copy stream itself may still be busy with `next`)
+  HIP_TRY(hipStreamSynchronize(CTX.stream));
+  if(a.host)
+  {
+    TRY(upload_validate(*a.x, a.host->sequences, a.host->bases, a.host->C, 16));
+    TRY(transcode(*a.x));
+  }
   return BWTM_OK;
 }
 
@@ -469,12 +544,9 @@ int download_samples(bwtm_index* x, u64* block_end, u64* cum)
     }
     return BWTM_OK;
   };
-  rc = body();
-  hipError_t e1 = hipStreamSynchronize(CTX.copy_stream), e2 = hipStreamSynchronize(CTX.stream);
+  rc = join_streams("sample download", body());
   for(int k = 0; k < 2; k++) { if(filled[k]) { (void)hipEventDestroy(filled[k]); } if(drained[k]) { (void)hipEventDestroy(drained[k]); } }
-  if(rc != BWTM_OK) { return rc; }
-  if(e1 != hipSuccess || e2 != hipSuccess) { return fail(BWTM_ENODEV, "sample download failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
-  return BWTM_OK;
+  return rc;
 }
 
 // Width of the compact sample fields: 1, 2 or 4 bytes when every block encodes fewer than 2^8 - 1 / 2^16 - 1 / 2^32 - 1 positions, else 8
@@ -536,12 +608,9 @@ int download_samples_compact(bwtm_index* x, T* fields, u64* anchors)
     }
     return BWTM_OK;
   };
-  int rc = body();
-  hipError_t e1 = hipStreamSynchronize(CTX.copy_stream), e2 = hipStreamSynchronize(CTX.stream);
+  const int rc = join_streams("sample download", body());
   for(int k = 0; k < 2; k++) { if(filled[k]) { (void)hipEventDestroy(filled[k]); } if(drained[k]) { (void)hipEventDestroy(drained[k]); } }
-  if(rc != BWTM_OK) { return rc; }
-  if(e1 != hipSuccess || e2 != hipSuccess) { return fail(BWTM_ENODEV, "sample download failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
-  return BWTM_OK;
+  return rc;
 }
 
 } // namespace

@@ -47,10 +47,16 @@ int interleave_chunks(const bwtm_index* a, const bwtm_index* b, bwtm_ra* ra, u64
   return BWTM_OK;                                                    // base_rel returns to the pool in stream order
 }
 
+// The header of the merge of a and b: n, m (bwt.cpp:305-306) and the first `entries` entries of C (fmi.cpp:367-368).
+void merged_header(const bwtm_index* a, const bwtm_index* b, u64* n, u64* m, u64* C, int entries = 8)
+{
+  *n = a->n + b->n; *m = a->m + b->m;
+  for(int c = 0; c < entries; c++) { C[c] = a->C[c] + b->C[c]; }
+}
+
 int interleave_impl(const bwtm_index* a, const bwtm_index* b, bwtm_ra* ra, bwtm_index* x)
 {
-  x->n = ra->n_out; x->m = a->m + b->m;                           // bwt.cpp:305-306
-  for(int c = 0; c < 8; c++) { x->C[c] = a->C[c] + b->C[c]; }     // fmi.cpp:367-368
+  merged_header(a, b, &x->n, &x->m, x->C);                        // (n == ra->n_out: check_interleave_args)
   x->nrecs = ra->nrecs_out; x->nsup = num_supers(x->n);
   TRY(x->recs.alloc(x->nrecs * 64));
   TRY(x->sup.alloc(x->nsup * SUP_STRIDE * sizeof(u64)));
@@ -132,65 +138,18 @@ int merge_host_impl(bwtm_index* a_dev, const bwtm_host_input* a_host, const bwtm
   bwtm_upload* pending_next = nullptr;
   bwtm_host_input b_desc;
   if(b_pending) { b = b_pending->x; b_pending->x = nullptr; b_desc = b_pending->host; b_host = &b_desc; }
-  else { b = new bwtm_index(); }
   auto body = [&]() -> int
   {
-    // The copies of both inputs are queued first (copy stream: b's chunks, then a's).  b's decode pass and scans run on the compute
-    // stream while b's later chunks arrive; the host then waits for b's scan results only -- a's bytes are still on the link --
-    // VALIDATES b's header against the stream, and only then queues b's transcode, which sizes its output from the header
-    // (a wrong `bases` or a non-canonical stream must never reach k_build_recs).  a follows the same way.
-    UploadEvents ev_a, ev_b_own;
-    UploadEvents& ev_b = (b_pending ? b_pending->events : ev_b_own);
-    if(!b_pending)
-    {
-      b->ctx = t_ctx; b->nbytes = b_host->nbytes; b->n = b_host->bases; b->m = b_host->sequences;
-      TRY(alloc_native(b->data, b_host->nbytes));
-      TRY(upload_prepare(b));
-    }
-    else if(b->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_pipelined: the pending upload lives in another context"); }
+    if(b_pending && b->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_pipelined: the pending upload lives in another context"); }
+    UploadEvents ev_a, ev_b;
+    UploadSlot sn;
     if(next)
     {
       pending_next = new bwtm_upload();
       pending_next->set(*next);
-      bwtm_index* nx = new bwtm_index();
-      pending_next->x = nx;
-      nx->ctx = t_ctx; nx->nbytes = next->nbytes; nx->n = next->bases; nx->m = next->sequences;
-      TRY(alloc_native(nx->data, next->nbytes));
-      TRY(upload_prepare(nx));
+      sn = {next, &pending_next->x, &pending_next->events};
     }
-    if(a_host)
-    {
-      a = new bwtm_index();
-      a->ctx = t_ctx; a->nbytes = a_host->nbytes; a->n = a_host->bases; a->m = a_host->sequences;
-      TRY(alloc_native(a->data, a_host->nbytes));
-      TRY(upload_prepare(a));
-    }
-    TRY(fork_copy_stream());                                        // recycled blocks may have queued users on the compute stream
-    if(!b_pending) { TRY(upload_copies(b, (b_host->nbytes > 0 ? b_host->data : (const u8*)""), ev_b)); }
-    if(a_host) { TRY(upload_copies(a, (a_host->nbytes > 0 ? a_host->data : (const u8*)""), ev_a)); }
-    if(next) { TRY(upload_copies(pending_next->x, (next->nbytes > 0 ? next->data : (const u8*)""), pending_next->events)); }   // under this merge's search
-    TRY(upload_decode(b, &ev_b));
-    TRY(upload_scan(b, 8));
-    hipEvent_t b_scanned = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&b_scanned, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(b_scanned, CTX.stream);
-    if(e == hipSuccess) { e = hipEventSynchronize(b_scanned); }
-    (void)hipEventDestroy(b_scanned);
-    if(e != hipSuccess) { return fail(BWTM_ENODEV, "upload failed: %s", hipGetErrorString(e)); }
-    TRY(upload_validate(b, b_host->sequences, b_host->bases, b_host->C, 8));
-    TRY(transcode(b));
-    if(a_host)
-    {
-      TRY(upload_decode(a, &ev_a));
-      TRY(upload_scan(a, 16));
-    }
-    // (the compute stream has waited for every chunk of a and b; the copy stream itself may still be busy with `next`)
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    if(a_host)
-    {
-      TRY(upload_validate(a, a_host->sequences, a_host->bases, a_host->C, 16));
-      TRY(transcode(a));
-    }
+    TRY(upload_pipelined({a_host, &a, &ev_a}, {b_host, &b, (b_pending ? &b_pending->events : &ev_b), b_pending != nullptr}, sn, false));
     if(a->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_chained: the index lives in another context"); }
     // the native bytes of the inputs are not needed any more (BlockArray::clearUntil, bwt.cpp:224-225)
     TRY(bwtm_index_drop_native(a)); TRY(bwtm_index_drop_native(b));
@@ -361,13 +320,9 @@ extern "C" int bwtm_upload_begin(const bwtm_host_input* in, bwtm_upload** out)
   ENTER(nullptr);
   bwtm_upload* u = new bwtm_upload();
   u->set(*in);
-  bwtm_index* x = new bwtm_index();
-  u->x = x;
-  x->ctx = t_ctx; x->nbytes = in->nbytes; x->n = in->bases; x->m = in->sequences;
-  int rc = alloc_native(x->data, in->nbytes);
-  if(rc == BWTM_OK) { rc = upload_prepare(x); }
+  int rc = upload_index(*in, &u->x);
   if(rc == BWTM_OK) { rc = fork_copy_stream(); }
-  if(rc == BWTM_OK) { rc = upload_copies(x, (in->nbytes > 0 ? in->data : (const u8*)""), u->events); }
+  if(rc == BWTM_OK) { rc = upload_copies(u->x, in->data, u->events); }
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.copy_stream); delete u; return rc; }
   *out = u;
   return BWTM_OK;

@@ -255,8 +255,7 @@ int merge_host_streamed_impl(bwtm_index* a_dev, const bwtm_host_input* a_host, c
   Streamer st;                                                       // owns a, b, ra, the slices and the staging: released on every path
   st.a = a_dev; st.want = want_samples; st.sink = sink; st.user = user; st.by_query = (g_tune.stream_samples_query != 0);
   std::memset(out, 0, sizeof(*out));
-  // Upload and transcode as merge_host_impl does (copy stream: b's chunks, then a's; b is decoded, validated and transcoded while a's bytes
-  // are still on the link) -- but b's native bytes go as soon as b is transcoded, not after a.
+  // Upload and transcode as merge_host_impl does (upload_pipelined) -- but b's native bytes go as soon as b is transcoded, not after a.
   if(g_tune.stream_upload)
   {
     // The chunked upload: b's chunks, then a's, through one ring; neither stream is ever resident as a whole.  One synchronisation for both.
@@ -268,54 +267,16 @@ int merge_host_streamed_impl(bwtm_index* a_dev, const bwtm_host_input* a_host, c
     TRY(rc); TRY(rj);
     TRY(ChunkedUpload::validate(st.b, b_host->sequences, b_host->bases, b_host->C, 8));
     if(a_host) { TRY(ChunkedUpload::validate(st.a, a_host->sequences, a_host->bases, a_host->C, 16)); }
-    if(st.a->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_streamed: the index lives in another context"); }
-    WHOLE_INDEX(st.a, "bwtm_merge_host_streamed");
-    TRY(bwtm_index_drop_native(st.a));
     st.peak = std::max(st.peak, up.peak);
   }
   else
   {
     UploadEvents ev_a, ev_b;
-    bwtm_index* b = new bwtm_index(); st.b = b;
-    b->ctx = t_ctx; b->nbytes = b_host->nbytes; b->n = b_host->bases; b->m = b_host->sequences;
-    TRY(alloc_native(b->data, b_host->nbytes));
-    TRY(upload_prepare(b));
-    if(a_host)
-    {
-      bwtm_index* a = new bwtm_index(); st.a = a;
-      a->ctx = t_ctx; a->nbytes = a_host->nbytes; a->n = a_host->bases; a->m = a_host->sequences;
-      TRY(alloc_native(a->data, a_host->nbytes));
-      TRY(upload_prepare(a));
-    }
-    TRY(fork_copy_stream());
-    TRY(upload_copies(b, (b_host->nbytes > 0 ? b_host->data : (const u8*)""), ev_b));
-    if(a_host) { TRY(upload_copies(st.a, (a_host->nbytes > 0 ? a_host->data : (const u8*)""), ev_a)); }
-    TRY(upload_decode(b, &ev_b));
-    TRY(upload_scan(b, 8));
-    hipEvent_t b_scanned = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&b_scanned, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(b_scanned, CTX.stream);
-    if(e == hipSuccess) { e = hipEventSynchronize(b_scanned); }
-    (void)hipEventDestroy(b_scanned);
-    if(e != hipSuccess) { return fail(BWTM_ENODEV, "upload failed: %s", hipGetErrorString(e)); }
-    TRY(upload_validate(b, b_host->sequences, b_host->bases, b_host->C, 8));
-    TRY(transcode(b));
-    TRY(bwtm_index_drop_native(b));
-    if(a_host)
-    {
-      TRY(upload_decode(st.a, &ev_a));
-      TRY(upload_scan(st.a, 16));
-    }
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    if(a_host)
-    {
-      TRY(upload_validate(st.a, a_host->sequences, a_host->bases, a_host->C, 16));
-      TRY(transcode(st.a));
-    }
-    if(st.a->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_streamed: the index lives in another context"); }
-    WHOLE_INDEX(st.a, "bwtm_merge_host_streamed");
-    TRY(bwtm_index_drop_native(st.a));
+    TRY(upload_pipelined({a_host, &st.a, &ev_a}, {b_host, &st.b, &ev_b}, {}, true));
   }
+  if(st.a->ctx != t_ctx) { return fail(BWTM_EINVAL, "bwtm_merge_host_streamed: the index lives in another context"); }
+  WHOLE_INDEX(st.a, "bwtm_merge_host_streamed");
+  TRY(bwtm_index_drop_native(st.a));
   const double t1 = now_ms();
   out->ms_upload = t1 - t0;
 
@@ -329,8 +290,7 @@ int merge_host_streamed_impl(bwtm_index* a_dev, const bwtm_host_input* a_host, c
   out->ms_search = t2 - t1;
 
   const u64 n = st.ra->n_out, nrecs = st.ra->nrecs_out;
-  out->sequences = a->m + b->m; out->bases = n;
-  for(int c = 0; c <= 6; c++) { out->C[c] = a->C[c] + b->C[c]; }
+  merged_header(a, b, &out->bases, &out->sequences, out->C, 7);
   st.n = n;
   st.tail[0] = n;
   for(int c = 1; c < 6; c++) { st.tail[c] = out->C[c + 1] - out->C[c]; }

@@ -128,12 +128,7 @@ struct ChunkedUpload
   }
 
   // The one synchronisation: the caller's buffers are free again, the totals are on the host.
-  int join()
-  {
-    hipError_t e1 = hipStreamSynchronize(CTX.copy_stream), e2 = hipStreamSynchronize(CTX.stream);
-    if(e1 != hipSuccess || e2 != hipSuccess) { return fail(BWTM_ENODEV, "upload failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); }
-    return BWTM_OK;
-  }
+  int join() { return join_streams("upload"); }
 
   // After join(): the header against the stream, with upload_validate's verdicts.  The index keeps records and super table only.
   static int validate(bwtm_index* x, u64 sequences, u64 bases, const u64* C, u32 slot)
@@ -151,7 +146,7 @@ int chunked_index(ChunkedUpload& up, const u8* data, u64 nbytes, u64 sequences, 
   bwtm_index* x = new bwtm_index();
   *out = x;                                                          // owned by the caller from here on, also on failure
   x->ctx = t_ctx; x->n = bases; x->m = sequences;
-  return up.queue(x, (nbytes > 0 ? data : (const u8*)""), nbytes, slot);
+  return up.queue(x, data, nbytes, slot);                            // (an empty stream queues no copy: `data` is never read)
 }
 
 } // namespace

@@ -235,6 +235,83 @@ def test_host_to_host_merge(gpu, oracle, chunks):
             hb.free()
 
 
+def test_wrong_header_is_refused_by_every_host_entry_point(gpu, oracle):
+    """A header that contradicts its stream, and a stream that is not canonical, on one input at a time (as input2 and as input1): every
+    entry point that takes host bytes -- the one-shot upload, the announced upload, the one-shot, pipelined and streamed merges, the last
+    in both upload forms -- refuses it with the text bwtm_index_upload gives for the same input, and a correct call through the same
+    entry point right after returns the oracle's bytes (the context is healthy, nothing was left queued).  Where the bad input is
+    input1 of the pipelined merge, the pending upload it consumes is the good input2."""
+    from test_gpu_upload_streamed import short_block
+    group_bytes = 62 * 64
+    fm = [oracle.FMI.from_text(oracle.generate_reads(4300 + k, 3000 + 200 * k, 100)) for k in range(2)]
+    m, _ = oracle.merge(fm[0].clone(), fm[1].clone(), threads=2)
+    assert all(f.nbytes > 5 * group_bytes for f in fm)               # several 62-block groups per stream
+    block = 3 * 62 + 5                                               # in the fourth chunk of one group
+    pinned, spoiled = [], []
+    for f in fm:
+        for store, bad in ((pinned, False), (spoiled, True)):
+            hb = gpu.HostBuffer(f.nbytes)
+            hb.array[:] = f.data
+            if bad:
+                hb.array[64 * block: 64 * block + 64] = short_block()
+            store.append(hb)
+    good = [(pinned[k].array, fm[k].sequences, fm[k].bases) for k in range(2)]
+
+    def streamed(a, b):
+        return gpu.merge_host_streamed(a, b, samples=0)[0]
+
+    def chunked(a, b):
+        gpu.tune("stream_upload", 1); gpu.tune("upload_chunk", group_bytes)
+        try:
+            return streamed(a, b)
+        finally:
+            gpu.tune("stream_upload", 0); gpu.tune("upload_chunk", 0)
+
+    def merged(a, b):
+        r = gpu.merge_host(a, b, samples=False)
+        data = r.data.copy()
+        r.free()
+        return data
+
+    def pipelined(a, b):
+        r, none = gpu.merge_host_pipelined(a=a, pending=gpu.upload_begin(*b), samples=False)
+        data = r.data.copy()
+        r.free()
+        return data
+
+    def index_bytes(ix):
+        data = ix.data()
+        ix.free()
+        return data
+
+    try:
+        for which in (1, 0):
+            f = fm[which]
+            cases = [("bases - 1", (pinned[which].array, f.sequences, f.bases - 1)), ("bases // 2", (pinned[which].array, f.sequences, f.bases // 2)),
+                     ("bases + 4096", (pinned[which].array, f.sequences, f.bases + 4096)), ("sequences + 1", (pinned[which].array, f.sequences + 1, f.bases)),
+                     ("short block", (spoiled[which].array, f.sequences, f.bases))]
+            for name, bad in cases:
+                with pytest.raises(gpu.BwtmError) as oneshot:
+                    gpu.Index.upload(*bad)
+                want = str(oneshot.value)
+                print("input%d, %s: %s" % (which + 1, name, want))
+                assert ("canonical" in want) == (name == "short block"), name
+                assert np.array_equal(index_bytes(gpu.Index.upload(*good[which])), f.data), name
+                with pytest.raises(gpu.BwtmError) as e:
+                    gpu.upload_begin(*bad).finish()
+                assert str(e.value) == want, name
+                assert np.array_equal(index_bytes(gpu.upload_begin(*good[which]).finish()), f.data), name
+                pair = ((bad, good[1]) if which == 0 else (good[0], bad))
+                for entry in (merged, pipelined, streamed, chunked):
+                    with pytest.raises(gpu.BwtmError) as e:
+                        entry(*pair)
+                    assert str(e.value) == want, (name, entry.__name__)
+                    assert np.array_equal(entry(*good), m.data), (name, entry.__name__)
+    finally:
+        for hb in pinned + spoiled:
+            hb.free()
+
+
 @pytest.mark.parametrize("chunk", [0, 4096])
 def test_pipelined_chain_of_host_merges(gpu, oracle, chunk):
     """bwt_merge in0 in1 in2 in3 as three bwtm_merge_host_pipelined calls: every merge announces the input of the next one, whose
