@@ -137,6 +137,7 @@ SYMBOLS = [
     ("bwtm_inverse_select_batch", C.c_int, [vp, p_u64, u64, p_u64, p_u8]),
     ("bwtm_find_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u64, p_u64]),
     ("bwtm_extract", C.c_int, [vp, u64, u64, p_u8]),
+    ("bwtm_sequences_extract", C.c_int, [vp, p_u64, u64, u64, u64, p_u64, p_u8, u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -590,6 +591,22 @@ def _u64(a):
     return a, a.ctypes.data_as(p_u64)
 
 
+class SequenceCount(int):
+    """What Index.sequences gives: the number of sequences, as the int it has always been -- and, called,
+    Index.sequences(ids=None, first=0, count=None, max_len=0) -> (offsets, text): the sequences themselves (Index.extract_sequences)."""
+
+    def __new__(cls, value, index):
+        self = super().__new__(cls, value)
+        self.index = index
+        return self
+
+    def __call__(self, ids=None, first=0, count=None, max_len=0):
+        return self.index.extract_sequences(ids, first, count, max_len)
+
+    def __reduce__(self):                 # copied or sent to another process it is the plain number (a handle does not travel)
+        return (int, (int(self),))
+
+
 class Index:
     """Device-resident FM-index (handle on bwtm_index)."""
 
@@ -648,7 +665,7 @@ class Index:
         return Index(out)
 
     bases = property(lambda s: int(lib().bwtm_index_bases(s.h)))
-    sequences = property(lambda s: int(lib().bwtm_index_sequences(s.h)))
+    sequences = property(lambda s: SequenceCount(lib().bwtm_index_sequences(s.h), s))
     nbytes = property(lambda s: int(lib().bwtm_index_bytes(s.h)))
     blocks = property(lambda s: int(lib().bwtm_index_blocks(s.h)))
 
@@ -737,6 +754,23 @@ class Index:
         out = np.zeros(count, dtype=np.uint8)
         check(lib().bwtm_extract(self.h, first, count, out.ctypes.data_as(p_u8)))
         return out
+
+    def extract_sequences(self, ids=None, first=0, count=None, max_len=0):
+        """Index.sequences(...): sequences by id (bwtm_sequences_extract): ids = an array of ids in any order, repeats allowed, or None for the ids
+        first .. first + count - 1 (count=None: up to the last sequence).  Returns (offsets uint64 [count + 1], text uint8): sequence j is
+        text[offsets[j]: offsets[j + 1]], comp values 1..5 in forward order.  One sizing call, then the extracting call."""
+        ip = None
+        if ids is not None:
+            ids, ip = _u64(ids)
+            count = ids.size
+        elif count is None:
+            count = max(self.sequences - int(first), 0)
+        offsets = np.zeros(int(count) + 1, dtype=np.uint64)
+        check(lib().bwtm_sequences_extract(self.h, ip, int(first), int(count), int(max_len), offsets.ctypes.data_as(p_u64), None, 0))
+        text = np.zeros(int(offsets[-1]), dtype=np.uint8)
+        if text.size > 0:
+            check(lib().bwtm_sequences_extract(self.h, ip, int(first), int(count), int(max_len), offsets.ctypes.data_as(p_u64), text.ctypes.data_as(p_u8), text.size))
+        return offsets, text
 
 
 class RankArray:

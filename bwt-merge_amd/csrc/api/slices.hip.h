@@ -229,9 +229,13 @@ extern "C" int bwtm_interleave_range(const bwtm_index* a, const bwtm_index* b, b
     TRY(s->sup.alloc(s->nsup * SUP_STRIDE * sizeof(u64)));
     if(a->windowed || b->windowed)
     {
-      // windows hold the records of this range only: the super rows the slice refers to, from inside the range (kernels/partition.hip.h)
+      // windows hold the records of this range only: the super rows the slice refers to, from inside the range (kernels/partition.hip.h).
+      // An empty range refers to no row, and bwtm_ra_finalize_range installs no count for its halo chunk: asked for that chunk's row, the
+      // kernel would take chunk_base's zero for the b offset and query position 0 of b, which a window that begins later does not hold (a
+      // read far in front of its records: a fault whenever nothing is mapped there).  q_base = q_end: no row is computed, all stay zero.
+      const u64 q_base = (rec_first < rec_last ? (s->rec_halo >> 6) << 6 : rec_last);
       LAUNCH("interleave_sup", k_interleave_sup_window, div_up(s->nsup, BLOCK_THREADS), BLOCK_THREADS, a->view(), b->view(), ra->chunk_base.as<const u64>(),
-        s->sup.as<u64>(), s->nsup, ra->super_boff.as<const u64>(), (s->rec_halo >> 6) << 6, rec_last);
+        s->sup.as<u64>(), s->nsup, ra->super_boff.as<const u64>(), q_base, rec_last);
     }
     else
     LAUNCH("interleave_sup", k_interleave_sup, div_up(s->nsup, BLOCK_THREADS), BLOCK_THREADS, a->view(), b->view(),

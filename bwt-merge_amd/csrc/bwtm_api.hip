@@ -13,6 +13,7 @@
     api/stream.hip.h    host-to-host merge whose second half runs slice by slice on one GPU, the result handed to the caller in pieces
     api/group.hip.h     the parts of a multi-GPU merge: shared control block (barrier, small all-gathers), exported arenas (raw pointer / HIP IPC)
     api/pmerge.hip.h    the merge over PARTITIONED records, one part per GPU: windows from byte shares, cuts, the routed search, the second half
+    api/sequences.hip.h sequences by id: lengths, offsets and text in batches of bounded device memory
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -51,3 +52,4 @@ using namespace bwtm;
 #include "api/partition.hip.h"
 #endif
 #include "api/ingest.hip.h"
+#include "api/sequences.hip.h"

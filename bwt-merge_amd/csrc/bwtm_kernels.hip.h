@@ -29,6 +29,9 @@
     k_piece_fields     the samples of one piece of a streamed merge, from the encoder's block starts and cum32 (kernels/stream.hip.h)
     k_rank_batch, k_inverse_select_batch, k_extract, k_find_batch
                        BWT::rank / inverse_select / extract, FMI::find  bwt.cpp:318-464, fmi.h:195-221
+    k_seq_lengths, k_seq_emit
+                       sequences by id: the LF walk from the endmarker, four lanes per sequence (kernels/sequences.hip.h; no counterpart
+                       in the reference, the inverse of k_ingest_*)
 */
 #pragma once
 
@@ -75,6 +78,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/transcode.hip.h"
 #include "kernels/queries.hip.h"
 #include "kernels/search_walk.hip.h"
+#include "kernels/sequences.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

@@ -144,6 +144,21 @@ public:
   }
   template<class Container> range_type find(const Container& pattern) const { return find(pattern.begin(), pattern.end()); }
 
+  // The sequences with the ids [ids.first, ids.second] as comp values 1..5 in forward order, endmarkers not included: sequence k of the
+  // range is text[offsets[k] .. offsets[k + 1]).  LF walks on the device (bwtm_sequences_extract: a sizing call, then the extracting one);
+  // no sequence may be longer than max_len (0: 65536).  The index goes to the device if it is not there, and stays.
+  void sequences(range_type ids, std::vector<size_type>& offsets, std::vector<byte_type>& text, size_type max_len = 0) const
+  {
+    const size_type count = (Range::empty(ids) ? 0 : Range::length(ids));
+    offsets.assign(count + 1, 0); text.clear();
+    if(count == 0) { return; }
+    bwtm_index* ix = bwt.onDevice(alpha.C);
+    gpuCheck(bwtm_sequences_extract(ix, nullptr, ids.first, count, max_len, offsets.data(), nullptr, 0), "FMI::sequences()");
+    text.resize(offsets[count]);
+    if(text.empty()) { return; }
+    gpuCheck(bwtm_sequences_extract(ix, nullptr, ids.first, count, max_len, offsets.data(), text.data(), text.size()), "FMI::sequences()");
+  }
+
   template<class Format> void serialize(const std::string& filename) const;
   template<class Format> void load(const std::string& filename);
 

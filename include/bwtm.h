@@ -157,6 +157,17 @@ int bwtm_find_batch(const bwtm_index* index, const uint8_t* patterns, const uint
                     uint64_t* out_sp, uint64_t* out_ep);
 /* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each. */
 int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_t* out);
+/* Sequences of the collection by id, as plain comp values 1..5 in forward order, endmarkers not included.
+   ids == NULL: the ids first_id .. first_id + count - 1; otherwise ids[0 .. count) in any order, repeats allowed (first_id ignored).
+   offsets[count + 1] always receives the exclusive prefix sums of the lengths (offsets[count] = bytes of text).
+   text == NULL or capacity == 0: sizes only.  Otherwise capacity >= offsets[count] (BWTM_EINVAL if not) and sequence j
+   occupies text[offsets[j] .. offsets[j + 1]); bytes beyond offsets[count] are not touched.
+   max_len: no sequence may be longer (0: 65536; at most 2^24); a longer one, or an id >= sequences, is BWTM_EINVAL and
+   bwtm_last_error() names the first offending id.  Works on any whole index (uploaded, merged, built; records suffice),
+   not on a window.  The call works in batches of the extract_batch knob (2^20 sequences): its device memory beyond the
+   index is that of one batch. */
+int bwtm_sequences_extract(const bwtm_index* index, const uint64_t* ids, uint64_t first_id, uint64_t count, uint64_t max_len,
+                           uint64_t* offsets, uint8_t* text, uint64_t capacity);
 
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
