@@ -464,30 +464,73 @@ public:
     sdsl_compat::SDVector::serialize(out, size(), std::vector<size_type>(block_end.begin(), block_end.end()));
   }
 
-  void load(std::istream& in)
+  // Every size in the file is compared with the bytes that are left before it sizes anything, and the samples must describe
+  // the data they came with: see checkSamples().
+  void load(Source& in)
   {
     dropDevice(); host_current = true; sample_width = 8;
     header.load(in);
-    if(!header.check()) { std::cerr << "BWT::load(): Invalid header!" << std::endl; std::exit(EXIT_FAILURE); }
-    size_type nbytes = 0; sdsl_compat::read_member(nbytes, in);
+    if(!header.check()) { in.refuse("Invalid header!"); }
+    const size_type nbytes = in.get<size_type>("the byte count of the data");
+    if(nbytes > in.remaining()) { in.truncated("the data", nbytes); }
     data.bytes.resizeUninitialized(nbytes);
-    in.read((char*)data.bytes.data(), nbytes);
-    in.ignore(data.blocks() * BlockArray::BLOCK_SIZE - nbytes);
+    in.read(data.bytes.data(), nbytes, "the data");
+    in.skip(data.blocks() * BlockArray::BLOCK_SIZE - nbytes, "the padding of the last data block");
     std::vector<size_type> rows[SIGMA];
     for(size_type c = 0; c < SIGMA; c++)
     {
-      size_type universe = 0, m_size = 0; std::vector<size_type> ones;
-      sdsl_compat::SDVector::load(in, universe, ones);
-      sdsl_compat::read_member(m_size, in);
+      size_type universe = 0; std::vector<size_type> ones;
+      sdsl_compat::SDVector::load(in, universe, ones, "a sample array");
+      const size_type m_size = in.get<size_type>("the size of a sample array");
+      if(m_size != ones.size()) { in.refuse("a sample array of " + std::to_string(ones.size()) + " blocks announces " + std::to_string(m_size)); }
       rows[c].assign(ones.size() + 1, 0);
-      for(size_type k = 0; k < ones.size(); k++) { rows[c][k + 1] = ones[k] - k; }
+      for(size_type k = 0; k < ones.size(); k++) { rows[c][k + 1] = ones[k] - k; }          // strictly increasing: ones[k] >= k
+      if(rows[c].size() != rows[0].size()) { in.refuse("the sample arrays do not have the same number of blocks"); }
     }
     cum_stride = rows[0].size();
     cum_flat.resizeUninitialized(SIGMA * cum_stride);
     for(size_type c = 0; c < SIGMA; c++) { std::copy(rows[c].begin(), rows[c].end(), cum_flat.begin() + c * cum_stride); }
     size_type universe = 0; std::vector<size_type> ends;
-    sdsl_compat::SDVector::load(in, universe, ends);
+    sdsl_compat::SDVector::load(in, universe, ends, "the block boundaries");
     block_end.assign(ends.begin(), ends.end());
+    const char* wrong = checkSamples();
+    if(wrong != nullptr) { in.refuse(wrong); }
+  }
+
+  // What the full-form samples of a loaded file must satisfy, in O(blocks); nullptr, or what is wrong.  (That the bytes of
+  // `data` decode to these samples is checked for the last block only: the rest would be a pass over the data.)
+  const char* checkSamples() const
+  {
+    const size_type nblocks = cum_stride - 1;
+    if(nblocks != (data.size() + SAMPLE_RATE - 1) / SAMPLE_RATE) { return "the samples are not for the number of 64-byte blocks the data has"; }
+    if(block_end.size() != nblocks) { return "the block boundaries are not for the number of blocks the sample arrays have"; }
+    size_type total = 0;
+    for(size_type c = 0; c < SIGMA; c++)
+    {
+      const size_type* row = cum_flat.data() + c * cum_stride;
+      if(row[0] != 0) { return "a sample array does not start at 0"; }
+      size_type decreases = 0;
+      for(size_type k = 0; k < nblocks; k++) { decreases |= (size_type)(row[k + 1] < row[k]); }
+      if(decreases != 0) { return "a sample array decreases"; }
+      if(row[nblocks] > size() - total) { return "the sample arrays count more symbols than the header's bases"; }
+      total += row[nblocks];
+    }
+    if(total != size()) { return "the sample arrays do not add up to the header's bases"; }
+    if(cum_flat[nblocks] != sequences()) { return "the endmarkers the samples count are not the header's sequences"; }
+    size_type disorder = 0;
+    for(size_type k = 1; k < nblocks; k++) { disorder |= (size_type)(block_end[k] <= block_end[k - 1]); }
+    if(disorder != 0) { return "the block boundaries are not strictly increasing"; }
+    if(nblocks > 0 && block_end[nblocks - 1] != size() - 1) { return "the last block does not end at the header's last position"; }
+    if(nblocks > 0)                                         // the one block whose length the byte count decides: it must decode to its samples
+    {
+      size_type seen[SIGMA] = {};
+      for(size_type rle_pos = (nblocks - 1) * SAMPLE_RATE; rle_pos < data.size(); ) { range_type run = Run::read(data, rle_pos); seen[run.first] += run.second; }
+      for(size_type c = 0; c < SIGMA; c++)
+      {
+        if(seen[c] != cum(c, nblocks) - cum(c, nblocks - 1)) { return "the last block of the data does not decode to what its samples count (wrong byte count?)"; }
+      }
+    }
+    return nullptr;
   }
 
   NativeHeader                   header;

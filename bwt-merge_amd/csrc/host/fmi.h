@@ -402,16 +402,32 @@ inline void FMI::serialize<NativeFormat>(const std::string& filename) const
 template<>
 inline void FMI::load<NativeFormat>(const std::string& filename)
 {
-  std::ifstream in(filename.c_str(), std::ios_base::binary);
-  if(!in) { std::cerr << "FMI::load(): Cannot open input file " << filename << std::endl; std::exit(EXIT_FAILURE); }
+  std::ifstream stream(filename.c_str(), std::ios_base::binary);
+  if(!stream) { std::cerr << "FMI::load(): Cannot open input file " << filename << std::endl; std::exit(EXIT_FAILURE); }
+  Source in(stream, filename, "FMI::load()");
   bwt.load(in);
   sdsl_compat::PackedVector c2c, c2ch, cc;
-  c2c.load(in, false, 8); c2ch.load(in, false, 8); cc.load(in, false, 64);
+  c2c.load(in, false, 8, "char2comp"); c2ch.load(in, false, 8, "comp2char"); cc.load(in, false, 64, "the C array");
+  alpha.sigma = in.get<size_type>("sigma");
+  if(in.remaining() != 0) { in.refuse(std::to_string(in.remaining()) + " bytes behind the last member"); }
+  // The alphabet is this format's: 256 / 6 / 7 entries, C the prefix sums of what the samples count, the header's order flag its order.
+  if(alpha.sigma != BWT::SIGMA || c2c.count != Alphabet::MAX_SIGMA || c2ch.count != BWT::SIGMA || cc.count != BWT::SIGMA + 1)
+  {
+    in.refuse("the alphabet is not one of " + std::to_string(BWT::SIGMA) + " symbols");
+  }
   alpha.char2comp.resize(c2c.count); alpha.comp2char.resize(c2ch.count); alpha.C.resize(cc.count);
   for(size_type k = 0; k < c2c.count; k++) { alpha.char2comp[k] = (byte_type)c2c.get(k); }
   for(size_type k = 0; k < c2ch.count; k++) { alpha.comp2char[k] = (byte_type)c2ch.get(k); }
   for(size_type k = 0; k < cc.count; k++) { alpha.C[k] = cc.get(k); }
-  sdsl_compat::read_member(alpha.sigma, in);
+  size_type before = 0;
+  for(size_type c = 0; c < BWT::SIGMA; c++)
+  {
+    if(alpha.C[c] != before) { in.refuse("the C array is not the prefix sums of the symbol counts"); }
+    before += bwt.count((comp_type)c);
+  }
+  if(alpha.C[BWT::SIGMA] != before) { in.refuse("the C array is not the prefix sums of the symbol counts"); }
+  for(size_type k = 0; k < Alphabet::MAX_SIGMA; k++) { if(alpha.char2comp[k] >= BWT::SIGMA) { in.refuse("char2comp maps a character outside the alphabet"); } }
+  if(bwt.header.flags != (std::uint32_t)identifyAlphabet(alpha)) { in.refuse("the header's flags are not the alphabetic order of the alphabet"); }
 }
 
 // Foreign formats (reference FMI::load / serialize<Format>, fmi.h:114-134; BWT::load<Format>, bwt.h:90-104).
@@ -421,8 +437,9 @@ inline void FMI::load<NativeFormat>(const std::string& filename)
 template<class Format>
 inline void FMI::load(const std::string& filename)
 {
-  std::ifstream in(filename.c_str(), std::ios_base::binary);
-  if(!in) { std::cerr << "BWT::load(): Cannot open input file " << filename << std::endl; std::exit(EXIT_FAILURE); }
+  std::ifstream stream(filename.c_str(), std::ios_base::binary);
+  if(!stream) { std::cerr << "BWT::load(): Cannot open input file " << filename << std::endl; std::exit(EXIT_FAILURE); }
+  Source in(stream, filename, std::string(Format::name()) + " loader");
   const Alphabet order_alpha = createAlphabet(Format::order());
   bwt.data.clear();
   RunBuffer run_buffer;
@@ -454,9 +471,16 @@ inline void FMI::serialize(const std::string& filename) const
   Format::encode(out, bwt.header, [&](auto&& f)
   {
     const BlockArray& data = bwt.hostData();
+    size_type left = bwt.size();
     for(size_type rle_pos = 0; rle_pos < data.size(); )
     {
       range_type run = Run::read(data, rle_pos);
+      if(run.second > left)                                 // damaged data: a run of 2^60 positions must not be written out
+      {
+        std::cerr << "FMI::serialize(): " << filename << ": the data decodes to more than the header's " << bwt.size() << " bases" << std::endl;
+        std::exit(EXIT_FAILURE);
+      }
+      left -= run.second;
       f((size_type)(Format::characters ? order_alpha.comp2char[run.first] : run.first), run.second);
     }
   });

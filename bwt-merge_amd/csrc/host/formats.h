@@ -57,6 +57,11 @@ struct NativeHeader
     sdsl_compat::read_member(tag, in); sdsl_compat::read_member(flags, in);
     sdsl_compat::read_member(sequences, in); sdsl_compat::read_member(bases, in);
   }
+  void load(Source& in)
+  {
+    tag = in.get<std::uint32_t>("the header"); flags = in.get<std::uint32_t>("the header");
+    sequences = in.get<std::uint64_t>("the header"); bases = in.get<std::uint64_t>("the header");
+  }
 };
 
 // Alphabets of the two alphabetic orders (formats.cpp:33-52): sorted = $ACGNT.
@@ -103,6 +108,7 @@ struct RopeHeader
   RopeHeader() : tag(DEFAULT_TAG) {}
   void serialize(std::ostream& out) const { sdsl_compat::write_member(tag, out); }
   void load(std::istream& in) { sdsl_compat::read_member(tag, in); }
+  void load(Source& in) { tag = in.get<std::uint32_t>("the header"); }
   bool check() const { return tag == DEFAULT_TAG; }
 };
 
@@ -124,44 +130,39 @@ struct SGAHeader
     sdsl_compat::read_member(tag, in); sdsl_compat::read_member(sequences, in); sdsl_compat::read_member(bases, in);
     sdsl_compat::read_member(bytes, in); sdsl_compat::read_member(flags, in);
   }
+  void load(Source& in)
+  {
+    tag = in.get<std::uint16_t>("the header"); sequences = in.get<std::uint64_t>("the header"); bases = in.get<std::uint64_t>("the header");
+    bytes = in.get<std::uint64_t>("the header"); flags = in.get<std::uint32_t>("the header");
+  }
   bool check() const { return tag == DEFAULT_TAG && flags == DEFAULT_FLAGS; }
 };
-
-inline size_type remainingBytes(std::istream& in)
-{
-  std::streamoff here = in.tellg();
-  in.seekg(0, std::ios_base::end);
-  std::streamoff end = in.tellg();
-  in.seekg(here);
-  return (size_type)(end - here);
-}
 
 namespace codec
 {
 
 const size_type CHUNK = MEGABYTE;
 
-// `bytes` bytes of the stream, one item each.
+// `bytes` bytes of the file, one item each; the file is refused if it does not hold them.
 template<class Emit>
-void decodeBytes(std::istream& in, size_type bytes, Emit&& emit)
+void decodeBytes(Source& in, size_type bytes, const char* what, Emit&& emit)
 {
-  std::vector<char> buffer(CHUNK);
-  for(size_type done = 0; done < bytes && in; )
+  if(bytes > in.remaining()) { in.truncated(what, bytes); }
+  std::vector<char> buffer(std::min(CHUNK, std::max(bytes, (size_type)1)));
+  for(size_type done = 0; done < bytes; )
   {
-    size_type want = std::min(CHUNK, bytes - done);
-    in.read(buffer.data(), want);
-    size_type got = (size_type)in.gcount();
-    for(size_type k = 0; k < got; k++) { emit((size_type)(byte_type)buffer[k], (size_type)1); }
-    done += got;
-    if(got < want) { break; }
+    size_type want = std::min((size_type)buffer.size(), bytes - done);
+    if(in.readSome(buffer.data(), want) != want) { in.truncated(what, want); }
+    for(size_type k = 0; k < want; k++) { emit((size_type)(byte_type)buffer[k], (size_type)1); }
+    done += want;
   }
 }
 
-// One byte per run; `split` maps a byte to (comp, length).
+// One byte per run; `split` maps a byte to (comp, length).  A byte of length 0 is handed on like any other (it adds no position).
 template<class Split, class Emit>
-void decodeRunBytes(std::istream& in, size_type bytes, Split&& split, Emit&& emit)
+void decodeRunBytes(Source& in, size_type bytes, const char* what, Split&& split, Emit&& emit)
 {
-  decodeBytes(in, bytes, [&](size_type code, size_type) { range_type run = split((byte_type)code); emit(run.first, run.second); });
+  decodeBytes(in, bytes, what, [&](size_type code, size_type) { range_type run = split((byte_type)code); emit(run.first, run.second); });
 }
 
 struct ByteWriter
@@ -202,7 +203,7 @@ struct PlainFormat
 {
   static AlphabeticOrder order() { return ORDER; }
   const static bool characters = true;
-  template<class Emit> static void decode(std::istream& in, Emit&& emit) { codec::decodeBytes(in, remainingBytes(in), emit); }
+  template<class Emit> static void decode(Source& in, Emit&& emit) { codec::decodeBytes(in, in.remaining(), "the characters", emit); }
   template<class Runs> static void encode(std::ostream& out, const NativeHeader&, Runs&& runs)
   {
     codec::ByteWriter w(out);
@@ -218,10 +219,15 @@ struct IntVector8Format
 {
   static AlphabeticOrder order() { return AO_SORTED; }
   const static bool characters = CHARACTERS;
-  template<class Emit> static void decode(std::istream& in, Emit&& emit)
+  template<class Emit> static void decode(Source& in, Emit&& emit)
   {
-    size_type bits = 0; sdsl_compat::read_member(bits, in);
-    codec::decodeBytes(in, bits / 8, emit);
+    const size_type bits = in.get<size_type>("the bit count");
+    if(bits % 8 != 0) { in.refuse("the bit count " + std::to_string(bits) + " is not a whole number of bytes"); }
+    const size_type bytes = bits / 8, padding = (8 - bytes % 8) % 8;  // int_vector stores whole 64-bit words, and the file ends with them
+    if(bytes > in.remaining()) { in.truncated("the vector", bytes); }
+    if(in.remaining() - bytes < padding) { in.truncated("the padding of the last word", padding); }
+    if(in.remaining() - bytes > padding) { in.refuse(std::to_string(in.remaining() - bytes - padding) + " bytes behind the vector's last word"); }
+    codec::decodeBytes(in, bytes, "the vector", emit);
   }
   template<class Runs> static void encode(std::ostream& out, const NativeHeader& header, Runs&& runs)
   {
@@ -242,11 +248,11 @@ struct RopeFormat
   static AlphabeticOrder order() { return AO_DEFAULT; }
   const static bool characters = false;
   const static size_type MAX_RUN = 31;
-  template<class Emit> static void decode(std::istream& in, Emit&& emit)
+  template<class Emit> static void decode(Source& in, Emit&& emit)
   {
     RopeHeader header; header.load(in);
-    if(!header.check()) { std::cerr << "RopeFormat::load(): Invalid header!" << std::endl; std::exit(EXIT_FAILURE); }
-    codec::decodeRunBytes(in, remainingBytes(in), [](byte_type code) { return range_type(code & 0x07, code >> 3); }, emit);
+    if(!header.check()) { in.refuse("Invalid header!"); }
+    codec::decodeRunBytes(in, in.remaining(), "the runs", [](byte_type code) { return range_type(code & 0x07, code >> 3); }, emit);
   }
   template<class Runs> static void encode(std::ostream& out, const NativeHeader&, Runs&& runs)
   {
@@ -267,11 +273,19 @@ struct SGAFormat
   static AlphabeticOrder order() { return AO_DEFAULT; }
   const static bool characters = false;
   const static size_type MAX_RUN = 31;
-  template<class Emit> static void decode(std::istream& in, Emit&& emit)
+  // Bytes behind the `bytes` run bytes the header announces are not looked at; the header's totals must be what the runs add up to.
+  template<class Emit> static void decode(Source& in, Emit&& emit)
   {
     SGAHeader header; header.load(in);
-    if(!header.check()) { std::cerr << "SGAFormat::load(): Invalid header!" << std::endl; std::exit(EXIT_FAILURE); }
-    codec::decodeRunBytes(in, header.bytes, [](byte_type code) { return range_type(code >> 5, code & 0x1F); }, emit);
+    if(!header.check()) { in.refuse("Invalid header!"); }
+    size_type sequences = 0, bases = 0;
+    codec::decodeRunBytes(in, header.bytes, "the runs", [](byte_type code) { return range_type(code >> 5, code & 0x1F); },
+      [&](size_type comp, size_type length) { bases += length; if(comp == 0 || comp >= 6) { sequences += length; } emit(comp, length); });   // (6 and 7 are loaded as 0)
+    if(sequences != header.sequences || bases != header.bases)
+    {
+      in.refuse("the header announces " + std::to_string(header.sequences) + " sequences and " + std::to_string(header.bases) + " bases, the runs hold "
+        + std::to_string(sequences) + " and " + std::to_string(bases));
+    }
   }
   template<class Runs> static void encode(std::ostream& out, const NativeHeader& info, Runs&& runs)
   {

@@ -1,0 +1,25 @@
+/*
+  The C ABI as host_load_test links it: exactly the functions that program's link asks for, none of which does anything.  There is
+  no device behind them: whatever would allocate, upload or download answers BWTM_ENODEV, sizes are 0, handles nullptr.  With
+  bwtm_host_alloc failing, HostArray falls back to malloc (support.h).
+*/
+#include <bwtm.h>
+
+extern "C"
+{
+
+const char* bwtm_last_error(void) { return "host_load_test is linked without a device library"; }
+int bwtm_host_alloc(uint64_t, void** out) { *out = nullptr; return BWTM_ENODEV; }
+void bwtm_host_free(void*) {}
+void bwtm_index_free(bwtm_index*) {}
+void bwtm_upload_free(bwtm_upload*) {}
+uint64_t bwtm_index_bytes(const bwtm_index*) { return 0; }
+uint64_t bwtm_index_blocks(const bwtm_index*) { return 0; }
+int bwtm_index_encode(bwtm_index*) { return BWTM_ENODEV; }
+int bwtm_index_drop_native(bwtm_index*) { return BWTM_ENODEV; }
+int bwtm_index_download_data(bwtm_index*, uint8_t*, uint64_t) { return BWTM_ENODEV; }
+int bwtm_index_download_samples(bwtm_index*, uint64_t*, uint64_t*) { return BWTM_ENODEV; }
+int bwtm_index_samples_width(bwtm_index*, int*) { return BWTM_ENODEV; }
+int bwtm_index_download_samples_compact(bwtm_index*, int, void*, uint64_t*) { return BWTM_ENODEV; }
+
+}

@@ -18,10 +18,78 @@
 
 #include <istream>
 #include <ostream>
+#include <sstream>
 #include "utils.h"
 
 namespace bwtmerge
 {
+
+/*
+  An input file as the loaders read it.  The stream's length is measured once, every read is checked against what is left and against
+  what arrived, and a file that cannot be what it claims to be is refused the way the "Invalid header!" paths refuse: one line on
+  std::cerr -- LOADER: FILE: what is wrong -- and exit(EXIT_FAILURE).  Nothing a file states (a size, a width, a count) sizes an
+  allocation before it has been compared with remaining().
+*/
+class Source
+{
+public:
+  Source(std::istream& stream, const std::string& file, const std::string& loader) : in(stream), name(file), where(loader), left(0)
+  {
+    in.seekg(0, std::ios_base::end);
+    const std::streamoff end = in.tellg();
+    in.seekg(0, std::ios_base::beg);
+    if(!in || end < 0) { refuse("cannot determine the size of the input (not a regular file?)"); }
+    left = (size_type)end;
+  }
+
+  [[noreturn]] void refuse(const std::string& what) const
+  {
+    std::cerr << where << ": " << name << ": " << what << std::endl;
+    std::exit(EXIT_FAILURE);
+  }
+  [[noreturn]] void truncated(const char* what, size_type wanted) const
+  {
+    std::ostringstream msg; msg << "truncated in " << what << " (" << wanted << " bytes wanted, " << left << " left)";
+    refuse(msg.str());
+  }
+
+  size_type remaining() const { return left; }
+
+  void read(void* to, size_type n, const char* what)
+  {
+    if(n > left) { truncated(what, n); }
+    if(n == 0) { return; }
+    in.read((char*)to, (std::streamsize)n);
+    if(!in || (size_type)in.gcount() != n) { truncated(what, n); }
+    left -= n;
+  }
+  // At most n bytes; the number that arrived (the byte-per-item formats read in chunks).
+  size_type readSome(void* to, size_type n)
+  {
+    n = std::min(n, left);
+    if(n == 0) { return 0; }
+    in.read((char*)to, (std::streamsize)n);
+    const size_type got = (size_type)in.gcount();
+    left -= got;
+    return got;
+  }
+  void skip(size_type n, const char* what)
+  {
+    if(n > left) { truncated(what, n); }
+    if(n == 0) { return; }
+    in.seekg((std::streamoff)n, std::ios_base::cur);
+    if(!in) { truncated(what, n); }
+    left -= n;
+  }
+  template<class T> T get(const char* what) { T v = T(); read(&v, sizeof(T), what); return v; }
+
+  std::istream& in;
+  const std::string name, where;
+
+private:
+  size_type left;
+};
+
 namespace sdsl_compat
 {
 
@@ -64,14 +132,41 @@ struct PackedVector
     if(dynamic_width) { std::uint8_t w = (std::uint8_t)width; write_member(w, out); }
     out.write((const char*)words.data(), ((bits + 63) / 64) * 8);
   }
-  void load(std::istream& in, bool dynamic_width, size_type fixed_width)
+
+  // The size fields of a serialized vector, checked: the width is 1 to 64, the bits are whole entries, the words are in the file.
+  struct Frame { size_type bits, width, count, bytes; };
+  static Frame frame(Source& in, bool dynamic_width, size_type fixed_width, const char* what)
   {
-    size_type bits = 0; read_member(bits, in);
-    width = fixed_width;
-    if(dynamic_width) { std::uint8_t w = 0; read_member(w, in); width = (w == 0 ? 1 : w); }
-    count = bits / width;
-    words.assign((bits + 63) / 64 + 1, 0);
-    in.read((char*)words.data(), ((bits + 63) / 64) * 8);
+    Frame f;
+    f.bits = in.get<size_type>(what);
+    f.width = fixed_width;
+    if(dynamic_width) { f.width = in.get<std::uint8_t>(what); }
+    if(f.width == 0 || f.width > 64) { refuse(in, what, "has a width of", f.width, "bits"); }
+    if(f.bits % f.width != 0) { refuse(in, what, "is not a whole number of entries:", f.bits, "bits"); }
+    f.count = f.bits / f.width;
+    f.bytes = (f.bits / 64 + (f.bits % 64 != 0 ? 1 : 0)) * 8;
+    if(f.bytes > in.remaining()) { in.truncated(what, f.bytes); }
+    return f;
+  }
+  [[noreturn]] static void refuse(const Source& in, const char* what, const char* problem, size_type value, const char* unit)
+  {
+    std::ostringstream msg; msg << what << " " << problem << " " << value << " " << unit;
+    in.refuse(msg.str());
+  }
+
+  void load(Source& in, bool dynamic_width, size_type fixed_width, const char* what)
+  {
+    const Frame f = frame(in, dynamic_width, fixed_width, what);
+    width = f.width; count = f.count;
+    words.assign(f.bytes / 8 + 1, 0);
+    in.read(words.data(), f.bytes, what);
+  }
+  // The same checks without keeping the entries; the number of entries.
+  static size_type skip(Source& in, bool dynamic_width, size_type fixed_width, const char* what)
+  {
+    const Frame f = frame(in, dynamic_width, fixed_width, what);
+    in.skip(f.bytes, what);
+    return f.count;
   }
 };
 
@@ -130,15 +225,23 @@ struct SelectMCL
     }
   }
 
-  // Skips a serialized select support (the facade rebuilds nothing from it).
-  static void skip(std::istream& in)
+  // Skips a serialized select support over a vector with `expected` selected bits (the facade rebuilds nothing from it): its
+  // framing is checked -- the argument count, one superblock entry per 4096 arguments, mini_or_long empty or one bit per
+  // superblock, 64 or 4096 entries per block -- its contents are not.
+  static void skip(Source& in, size_type expected, const char* what)
   {
-    size_type arg_cnt = 0; read_member(arg_cnt, in);
+    const size_type arg_cnt = in.get<size_type>(what);
+    if(arg_cnt != expected) { PackedVector::refuse(in, what, "counts", arg_cnt, "arguments, the vector has another number"); }
     if(arg_cnt == 0) { return; }
-    size_type sb = (arg_cnt + 4095) / 4096;
-    PackedVector v; v.load(in, true, 0);
-    PackedVector mini_or_long; mini_or_long.load(in, false, 1);
-    for(size_type s = 0; s < sb; s++) { v.load(in, true, 0); }
+    const size_type sb = (arg_cnt + 4095) / 4096;
+    if(PackedVector::skip(in, true, 0, what) != sb) { in.refuse(std::string(what) + " does not have one superblock entry per 4096 arguments"); }
+    const size_type flagged = PackedVector::skip(in, false, 1, what);
+    if(flagged != 0 && flagged != sb) { in.refuse(std::string(what) + " does not have one mini_or_long bit per superblock"); }
+    for(size_type s = 0; s < sb; s++)
+    {
+      const size_type entries = PackedVector::skip(in, true, 0, what);
+      if(entries != 64 && entries != 4096) { PackedVector::refuse(in, what, "has a block of", entries, "entries (64 or 4096 expected)"); }
+    }
   }
 };
 
@@ -165,25 +268,41 @@ struct SDVector
     SelectMCL::serialize(out, high, false);
   }
 
-  static void load(std::istream& in, size_type& size, std::vector<size_type>& ones)
+  // `what` names the member in messages.  What sd_vector's builder guarantees is checked: wl < 64 is the width of the m low
+  // parts, wl = logn - logm by the rule above, high has m + 2^logm bits of which exactly m are set, and the positions are
+  // strictly increasing below `size`; so are the argument counts of the two select supports.
+  static void load(Source& in, size_type& size, std::vector<size_type>& ones, const char* what)
   {
-    std::uint8_t wl = 0;
-    read_member(size, in); read_member(wl, in);
+    size = in.get<size_type>(what);
+    const size_type wl = in.get<std::uint8_t>(what);
+    if(wl >= 64) { PackedVector::refuse(in, what, "has low parts of", wl, "bits"); }
     PackedVector low, high;
-    low.load(in, true, 0); high.load(in, false, 1);
-    SelectMCL::skip(in); SelectMCL::skip(in);
-    ones.clear(); ones.reserve(low.count);
-    size_type k = 0, nbits = high.bit_size();
-    for(size_type w = 0; w * 64 < nbits && k < low.count; w++)
+    low.load(in, true, 0, what);
+    const size_type m = low.count;
+    size_type logm = hi(m) + 1, logn = hi(size) + 1;
+    if(logm == logn) { logm--; }
+    if(low.width != wl || wl != logn - logm) { PackedVector::refuse(in, what, "has low parts of", low.width, "bits that do not follow from its size fields"); }
+    high.load(in, false, 1, what);
+    const size_type nbits = high.bit_size();
+    if(nbits != m + ((size_type)1 << logm)) { PackedVector::refuse(in, what, "has", nbits, "high bits that do not follow from its size fields"); }
+    ones.assign(m, 0);
+    size_type k = 0, disorder = 0, before = 0;            // (the order is checked on the way, without a branch per entry)
+    for(size_type w = 0; w * 64 < nbits; w++)
     {
       std::uint64_t word = high.words[w];
-      while(word != 0 && k < low.count)
+      if((w + 1) * 64 > nbits) { word &= (~(std::uint64_t)0) >> (64 - (nbits - w * 64)); }
+      if(k + (size_type)__builtin_popcountll(word) > m) { k = m + 1; break; }
+      while(word != 0)
       {
         const size_type pos = w * 64 + (size_type)__builtin_ctzll(word); word &= word - 1;
-        if(pos >= nbits) { break; }
-        ones.push_back(((pos - k) << wl) | low.get(k)); k++;
+        const size_type value = ((pos - k) << wl) | low.get(k);
+        disorder |= (size_type)(value < before) | (size_type)(value >= size);
+        ones[k] = value; before = value + 1; k++;
       }
     }
+    if(k != m) { PackedVector::refuse(in, what, "does not have one high bit for each of its", m, "low parts"); }
+    if(disorder != 0) { PackedVector::refuse(in, what, "is not strictly increasing below its size of", size, ""); }
+    SelectMCL::skip(in, m, what); SelectMCL::skip(in, nbits - m, what);
   }
 };
 

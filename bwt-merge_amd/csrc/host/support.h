@@ -172,11 +172,13 @@ public:
 // 7 data bits per byte, least significant group first, high bit = "continues".
 struct ByteCode
 {
+  // i < array.size().  A value takes at most 10 bytes; a continuation bit on the 10th, or on the last byte of the array (damaged
+  // data: the writer produces neither), ends the value there, so no read leaves the array and no shift reaches 64.
   template<class ByteArray>
   static size_type read(const ByteArray& array, size_type& i)
   {
     size_type shift = 0, value = array[i] & 0x7F;
-    while(array[i] & 0x80) { i++; shift += 7; value += ((size_type)(array[i] & 0x7F)) << shift; }
+    while((array[i] & 0x80) && shift + 7 < 64 && i + 1 < array.size()) { i++; shift += 7; value += ((size_type)(array[i] & 0x7F)) << shift; }
     i++;
     return value;
   }
@@ -200,11 +202,16 @@ struct Run
   static byte_type encodeBasic(comp_type comp, size_type length) { return (byte_type)(comp + SIGMA * (length - 1)); }
   static range_type decodeBasic(byte_type code) { return range_type(code % SIGMA, code / SIGMA + 1); }
 
+  constexpr static size_type PAST_END = (size_type)1 << 62;
+
+  // Reading at or past the end of the array (only data that disagrees with its samples leads a query there) yields an endmarker
+  // run of PAST_END positions, which ends every loop over positions; a head that announces an extension as the last byte has none.
   template<class ByteArray>
   static range_type read(const ByteArray& array, size_type& i)
   {
+    if(i >= array.size()) { i++; return range_type(0, +PAST_END); }
     range_type run = decodeBasic(array[i]); i++;
-    if(run.second >= MAX_RUN) { run.second += ByteCode::read(array, i); }
+    if(run.second >= MAX_RUN && i < array.size()) { run.second += ByteCode::read(array, i); }
     return run;
   }
 
