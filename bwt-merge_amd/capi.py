@@ -138,6 +138,11 @@ SYMBOLS = [
     ("bwtm_find_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u64, p_u64]),
     ("bwtm_extract", C.c_int, [vp, u64, u64, p_u8]),
     ("bwtm_sequences_extract", C.c_int, [vp, p_u64, u64, u64, u64, p_u64, p_u8, u64]),
+    ("bwtm_locator_create", C.c_int, [vp, u64, C.POINTER(vp)]),
+    ("bwtm_locator_free", None, [vp]),
+    ("bwtm_locator_bytes", u64, [vp]),
+    ("bwtm_locate_batch", C.c_int, [vp, p_u64, u64, p_u64, p_u64]),
+    ("bwtm_locate_ranges", C.c_int, [vp, p_u64, p_u64, u64, u64, p_u64, p_u64, p_u64, u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -771,6 +776,69 @@ class Index:
         if text.size > 0:
             check(lib().bwtm_sequences_extract(self.h, ip, int(first), int(count), int(max_len), offsets.ctypes.data_as(p_u64), text.ctypes.data_as(p_u8), text.size))
         return offsets, text
+
+    def locator(self, max_len=0):
+        """The table that turns BWT positions into (sequence id, offset) (bwtm_locator_create).  The locator borrows this index."""
+        return Locator(self, max_len)
+
+
+class Locator:
+    """From BWT positions of an index to (sequence id, offset of the suffix in that sequence) (handle on bwtm_locator).  It keeps a reference to
+    the index it borrows; free it before the index is consumed by a merge."""
+
+    def __init__(self, index, max_len=0):
+        out = vp()
+        check(lib().bwtm_locator_create(index.h, int(max_len), C.byref(out)))
+        self.h = out
+        self.index = index
+
+    nbytes = property(lambda s: int(lib().bwtm_locator_bytes(s.h)))
+
+    def free(self):
+        if self.h:
+            lib().bwtm_locator_free(self.h)
+            self.h = None
+            self.index = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def locate(self, positions):
+        """(ids, offsets) of an array of BWT positions."""
+        if not self.h:
+            raise BwtmError("the locator has been freed")
+        positions, pp = _u64(positions)
+        ids = np.zeros(positions.size, dtype=np.uint64)
+        offs = np.zeros(positions.size, dtype=np.uint64)
+        check(lib().bwtm_locate_batch(self.h, pp, positions.size, ids.ctypes.data_as(p_u64), offs.ctypes.data_as(p_u64)))
+        return ids, offs
+
+    def locate_ranges(self, sp, ep, max_hits=0):
+        """(hit_offsets [count + 1], ids, offsets) of closed ranges [sp, ep] (sp > ep: empty): the hits of range r are
+        [hit_offsets[r], hit_offsets[r + 1]) in ascending BWT position.  One sizing call, then the locating call."""
+        if not self.h:
+            raise BwtmError("the locator has been freed")
+        sp, spp = _u64(sp)
+        ep, epp = _u64(ep)
+        assert sp.size == ep.size
+        hit_offsets = np.zeros(sp.size + 1, dtype=np.uint64)
+        check(lib().bwtm_locate_ranges(self.h, spp, epp, sp.size, int(max_hits), hit_offsets.ctypes.data_as(p_u64), None, None, 0))
+        total = int(hit_offsets[-1])
+        ids = np.zeros(total, dtype=np.uint64)
+        offs = np.zeros(total, dtype=np.uint64)
+        if total > 0:
+            check(lib().bwtm_locate_ranges(self.h, spp, epp, sp.size, int(max_hits), hit_offsets.ctypes.data_as(p_u64), ids.ctypes.data_as(p_u64),
+                                           offs.ctypes.data_as(p_u64), total))
+        return hit_offsets, ids, offs
+
+    def locate_patterns(self, patterns, max_hits=0):
+        """Every occurrence of every pattern (sequences of comp values): find, the sizing call, the locating call.  Returns
+        (hit_offsets, ids, offsets); pattern k occurs at offset offsets[h] of sequence ids[h] for h in [hit_offsets[k], hit_offsets[k + 1])."""
+        sp, ep = self.index.find(patterns)
+        return self.locate_ranges(sp, ep, max_hits)
 
 
 class RankArray:

@@ -104,6 +104,7 @@ struct Tuning
   long long stream_samples_query = 0;     // bwtm_merge_host_streamed: 1 = the samples' counts from one rank query per block start (k_block_cum_slice) instead of the encoder's cum32: the cross-check
   long long stream_upload = 0;            // bwtm_merge_host_streamed: 1 = the host inputs through the chunked upload (api/upload_stream.hip.h): no native stream resident as a whole
   long long extract_batch = 1ll << 20;    // bwtm_sequences_extract: sequences per batch (bounds the device memory of the call beyond the index)
+  long long locate_batch = 1ll << 20;     // bwtm_locator_create / bwtm_locate_*: sequences / hits per batch (at most 2^28; bounds the device memory beyond the index and the table)
   long long ingest_verify = 0;            // 1 = the builder checks every leaf's suffix order against the reads (one extra pass of gathers per leaf)
 #ifdef BWTM_DIAGNOSTICS
   long long walk_emit = 0;       // 0 = real emit; 1 / 2 timing-only variants of the emit (see diagnostics.hip.h)
@@ -702,6 +703,7 @@ int tune_set(const char* key, long long value)
   else if(k == "stream_upload") { g_tune.stream_upload = (value != 0); }
   else if(k == "ingest_verify") { g_tune.ingest_verify = (value != 0); }
   else if(k == "extract_batch") { g_tune.extract_batch = (value > 0 ? value : (1ll << 20)); }
+  else if(k == "locate_batch") { g_tune.locate_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }
   else if(k == "recs_uniform") { g_tune.recs_uniform = (value > 0 ? 1 : (value < 0 ? -1 : 0)); }
   else if(k == "recs_window") { g_tune.recs_window = (value == 8192 || value == 16384 || value == 32768 ? value : 0); }

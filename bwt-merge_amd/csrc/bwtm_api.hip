@@ -14,6 +14,7 @@
     api/group.hip.h     the parts of a multi-GPU merge: shared control block (barrier, small all-gathers), exported arenas (raw pointer / HIP IPC)
     api/pmerge.hip.h    the merge over PARTITIONED records, one part per GPU: windows from byte shares, cuts, the routed search, the second half
     api/sequences.hip.h sequences by id: lengths, offsets and text in batches of bounded device memory
+    api/locate.hip.h    positions to (sequence id, offset): the locator's table, positions and ranges located in batches
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -53,3 +54,4 @@ using namespace bwtm;
 #endif
 #include "api/ingest.hip.h"
 #include "api/sequences.hip.h"
+#include "api/locate.hip.h"

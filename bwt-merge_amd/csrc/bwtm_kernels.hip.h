@@ -32,6 +32,9 @@
     k_seq_lengths, k_seq_emit
                        sequences by id: the LF walk from the endmarker, four lanes per sequence (kernels/sequences.hip.h; no counterpart
                        in the reference, the inverse of k_ingest_*)
+    k_locate_build, k_locate_check, k_locate
+                       from a BWT position to (sequence id, offset): the same walk from any position, and one table per index that
+                       numbers the whole-sequence suffixes (kernels/locate.hip.h; the step the reference's queries leave to the host)
 */
 #pragma once
 
@@ -79,6 +82,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/queries.hip.h"
 #include "kernels/search_walk.hip.h"
 #include "kernels/sequences.hip.h"
+#include "kernels/locate.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

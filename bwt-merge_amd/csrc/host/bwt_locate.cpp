@@ -1,0 +1,119 @@
+/*
+  bwt_locate -- the occurrences of patterns in the reads of a BWT file: for every pattern, the sequences that contain it and the offsets
+  at which it starts.  The reference has no such tool.  The backward searches run on the GPU in one batch (bwtm_find_batch), and the
+  positions of every range become (sequence, offset) by LF walks on the GPU (Locator, bwtm_locate_ranges).  Patterns are read, one per
+  line, and mapped exactly as `bwt_merge -v` reads them.  The output holds one line per hit,
+      pattern_number <TAB> sequence <TAB> offset        (all 0-based)
+  in the order of the patterns and, within a pattern, sorted by (sequence, offset): two runs compare with cmp.
+  Sequence k of an index built by bwt_ingest, or merged from such indexes by bwt_merge, is read k of the input(s) in order.
+*/
+#include <unistd.h>
+
+#include "fmi.h"
+
+using namespace bwtmerge;
+
+size_type Parallel::max_threads = std::max(1u, std::thread::hardware_concurrency());
+
+static void printUsage()
+{
+  std::cerr << "Usage: bwt_locate [options] input patterns output" << std::endl << std::endl;
+  std::cerr << "Options:" << std::endl;
+  std::cerr << "  -g N           Use GPU N (default: 0)" << std::endl;
+  std::cerr << "  -i format      Read the input in the given format (default: native)" << std::endl;
+  std::cerr << "  -m N           Longest sequence the input may hold (default: 65536, at most 16777216)" << std::endl;
+  std::cerr << "  -x N           Write at most N hits per pattern: the first N positions of its range (default: all)" << std::endl << std::endl;
+  printFormats(std::cerr);
+}
+
+// One pattern per line, empty lines skipped (readRows of bwt_merge.cpp).
+static size_type readRows(const std::string& filename, std::vector<std::string>& rows)
+{
+  std::ifstream in(filename.c_str(), std::ios_base::binary);
+  if(!in) { std::cerr << "bwt_locate: Cannot open pattern file " << filename << std::endl; std::exit(EXIT_FAILURE); }
+  size_type chars = 0;
+  for(std::string line; std::getline(in, line); ) { if(!line.empty()) { rows.push_back(line); chars += line.length(); } }
+  return chars;
+}
+
+int main(int argc, char** argv)
+{
+  if(argc < 2) { printUsage(); std::exit(EXIT_SUCCESS); }
+
+  std::cout << "BWT locate" << std::endl << std::endl;
+
+  int device = 0;
+  std::string input_tag = NativeFormat::tag();
+  size_type max_len = 0, max_hits = 0;
+  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:")) != -1; )
+  {
+    switch(c)
+    {
+    case 'g': device = std::stoi(optarg); break;
+    case 'i':
+      input_tag = optarg;
+      if(!formatExists(input_tag)) { std::cerr << "bwt_locate: Invalid input format: " << input_tag << std::endl; std::exit(EXIT_FAILURE); }
+      break;
+    case 'm': max_len = std::stoull(optarg); break;
+    case 'x': max_hits = std::stoull(optarg); break;
+    default: std::exit(EXIT_FAILURE);
+    }
+  }
+  if(optind + 2 >= argc) { std::cerr << "bwt_locate: Input, pattern and output files must be specified" << std::endl; std::exit(EXIT_FAILURE); }
+  std::string input_name = argv[optind], pattern_name = argv[optind + 1], output_name = argv[optind + 2];
+  std::cout << "Input:    " << input_name << " (" << input_tag << ")" << std::endl;
+  std::cout << "Patterns: " << pattern_name << std::endl;
+  std::cout << "Output:   " << output_name << " (pattern, sequence, offset)" << std::endl << std::endl;
+
+  double start = readTimer();
+  gpuCheck(bwtm_init(device), "bwt_locate");
+  std::vector<std::string> patterns;
+  const size_type chars = readRows(pattern_name, patterns);
+  FMI fmi; load(fmi, input_name, input_tag);
+  printSize("FMI", sizeInBytes(fmi), fmi.size());
+  std::cout << std::endl;
+
+  std::ofstream out(output_name.c_str(), std::ios_base::binary);
+  if(!out) { std::cerr << "bwt_locate: Cannot open output file " << output_name << std::endl; std::exit(EXIT_FAILURE); }
+  size_type found = 0, total = 0;
+  if(!patterns.empty())
+  {
+    std::vector<byte_type> text; text.reserve(chars);
+    std::vector<uint64_t> offsets(patterns.size() + 1, 0), sp(patterns.size()), ep(patterns.size());
+    for(size_type k = 0; k < patterns.size(); k++)
+    {
+      for(char ch : patterns[k]) { text.push_back(fmi.alpha.char2comp[(byte_type)ch]); }
+      offsets[k + 1] = text.size();
+    }
+    bwtm_index* ix = fmi.bwt.onDevice(fmi.alpha.C);
+    gpuCheck(bwtm_find_batch(ix, text.data(), offsets.data(), patterns.size(), sp.data(), ep.data()), "bwt_locate");
+    std::vector<range_type> ranges(patterns.size());
+    for(size_type k = 0; k < patterns.size(); k++) { ranges[k] = range_type(sp[k], ep[k]); }
+
+    Locator locator(fmi, max_len);
+    std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
+    locator.locate(ranges, hit_offsets, hits, max_hits);
+    total = hits.size();
+    std::string lines;
+    for(size_type k = 0; k < patterns.size(); k++)
+    {
+      if(hit_offsets[k + 1] == hit_offsets[k]) { continue; }
+      found++;
+      std::sort(hits.begin() + hit_offsets[k], hits.begin() + hit_offsets[k + 1]);
+      lines.clear();
+      for(size_type h = hit_offsets[k]; h < hit_offsets[k + 1]; h++)
+      {
+        lines += std::to_string(k); lines += '\t'; lines += std::to_string(hits[h].first); lines += '\t'; lines += std::to_string(hits[h].second); lines += '\n';
+      }
+      out.write(lines.data(), (std::streamsize)lines.size());
+    }
+  }
+  out.close();
+  if(!out) { std::cerr << "bwt_locate: Writing to " << output_name << " failed" << std::endl; std::exit(EXIT_FAILURE); }
+  double seconds = readTimer() - start;
+
+  std::cout << "Located " << patterns.size() << " patterns: " << found << " found, " << total << " hits" << std::endl << std::endl;
+  std::cout << "Patterns located in " << seconds << " seconds" << std::endl << std::endl;
+  std::cout << "Memory usage: " << inGigabytes(memoryUsage()) << " GB" << std::endl << std::endl;
+  return 0;
+}

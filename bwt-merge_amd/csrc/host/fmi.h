@@ -166,6 +166,53 @@ public:
   Alphabet alpha;
 };
 
+// From BWT positions of an FMI back to its collection: (sequence id, offset of the suffix in that sequence) for the positions of a range, as
+// FMI::find returns it (bwtm_locator_create, bwtm_locate_ranges: a sizing call, then the locating one).  The index goes to the device if it
+// is not there, and stays; the table of `sequences` 64-bit entries is built there by one LF walk per sequence.  The locator borrows the FMI's
+// device copy: build it after the last merge that involves the FMI, and drop it before the FMI.  No sequence may be longer than max_len
+// (0: 65536).
+class Locator
+{
+public:
+  typedef BWT::size_type size_type;
+  typedef std::pair<size_type, size_type> hit_type;                 // (sequence, offset)
+
+  explicit Locator(const FMI& fmi, size_type max_len = 0)
+  {
+    gpuCheck(bwtm_locator_create(fmi.bwt.onDevice(fmi.alpha.C), max_len, &this->handle), "Locator::Locator()");
+  }
+  ~Locator() { bwtm_locator_free(this->handle); }
+  Locator(const Locator&) = delete; Locator& operator=(const Locator&) = delete;
+
+  size_type bytes() const { return bwtm_locator_bytes(this->handle); }
+
+  // The hits of one range in ascending BWT position; max_hits > 0 keeps the first max_hits.
+  std::vector<hit_type> locate(range_type range, size_type max_hits = 0) const
+  {
+    std::vector<size_type> hit_offsets; std::vector<hit_type> hits;
+    this->locate(std::vector<range_type>(1, range), hit_offsets, hits, max_hits);
+    return hits;
+  }
+
+  // The hits of every range: those of range r are hits[hit_offsets[r] .. hit_offsets[r + 1]).
+  void locate(const std::vector<range_type>& ranges, std::vector<size_type>& hit_offsets, std::vector<hit_type>& hits, size_type max_hits = 0) const
+  {
+    std::vector<uint64_t> sp(ranges.size()), ep(ranges.size());
+    for(size_type r = 0; r < ranges.size(); r++) { sp[r] = ranges[r].first; ep[r] = ranges[r].second; }
+    hit_offsets.assign(ranges.size() + 1, 0); hits.clear();
+    gpuCheck(bwtm_locate_ranges(this->handle, sp.data(), ep.data(), ranges.size(), max_hits, hit_offsets.data(), nullptr, nullptr, 0), "Locator::locate()");
+    const size_type total = hit_offsets[ranges.size()];
+    if(total == 0) { return; }
+    std::vector<uint64_t> ids(total), offsets(total);
+    gpuCheck(bwtm_locate_ranges(this->handle, sp.data(), ep.data(), ranges.size(), max_hits, hit_offsets.data(), ids.data(), offsets.data(), total), "Locator::locate()");
+    hits.resize(total);
+    for(size_type h = 0; h < total; h++) { hits[h] = hit_type(ids[h], offsets[h]); }
+  }
+
+private:
+  bwtm_locator* handle = nullptr;
+};
+
 // Search phase (buildRA, reference fmi.cpp:272-334) as a free function: makes sure a and b are on the device and
 // fills a device rank array; parameters.sequence_blocks splits the sequences of b.
 inline void buildRA(const FMI& a, const FMI& b, const MergeParameters& parameters, RankArray& ra)

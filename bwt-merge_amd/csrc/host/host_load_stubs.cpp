@@ -1,5 +1,5 @@
 /*
-  The C ABI as host_load_test links it: exactly the functions that program's link asks for, none of which does anything.  There is
+  The C ABI as host_load_test links it: the functions that program's link asks for and the locator's entry points (fmi.h), none of which does anything.  There is
   no device behind them: whatever would allocate, upload or download answers BWTM_ENODEV, sizes are 0, handles nullptr.  With
   bwtm_host_alloc failing, HostArray falls back to malloc (support.h).
 */
@@ -21,5 +21,11 @@ int bwtm_index_download_data(bwtm_index*, uint8_t*, uint64_t) { return BWTM_ENOD
 int bwtm_index_download_samples(bwtm_index*, uint64_t*, uint64_t*) { return BWTM_ENODEV; }
 int bwtm_index_samples_width(bwtm_index*, int*) { return BWTM_ENODEV; }
 int bwtm_index_download_samples_compact(bwtm_index*, int, void*, uint64_t*) { return BWTM_ENODEV; }
+// the Locator of fmi.h
+int bwtm_locator_create(const bwtm_index*, uint64_t, bwtm_locator** out) { *out = nullptr; return BWTM_ENODEV; }
+void bwtm_locator_free(bwtm_locator*) {}
+uint64_t bwtm_locator_bytes(const bwtm_locator*) { return 0; }
+int bwtm_locate_batch(const bwtm_locator*, const uint64_t*, uint64_t, uint64_t*, uint64_t*) { return BWTM_ENODEV; }
+int bwtm_locate_ranges(const bwtm_locator*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
 
 }

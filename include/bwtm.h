@@ -169,6 +169,32 @@ int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_
 int bwtm_sequences_extract(const bwtm_index* index, const uint64_t* ids, uint64_t first_id, uint64_t count, uint64_t max_len,
                            uint64_t* offsets, uint8_t* text, uint64_t capacity);
 
+/* From BWT positions back to the collection: position p is the suffix that starts at offset o of sequence id (o = the length
+   of the sequence: its endmarker suffix, p < sequences).  A locator is one table of `sequences` 64-bit entries on the device
+   (bwtm_locator_bytes; 8 GB for 10^9 reads), built by one LF walk per sequence; a located position costs one walk to the
+   start of its sequence and one table entry.  Works on any whole index (uploaded, merged, built; records suffice), not on
+   a window.  max_len as in bwtm_sequences_extract (0: 65536; at most 2^24): a longer sequence is BWTM_EINVAL and
+   bwtm_last_error() names it; an index whose walks do not give every sequence a start of its own is refused as damaged.
+   The locator BORROWS the index: the index must outlive it and must not be consumed (bwtm_merge_consume) meanwhile; after a
+   merge, build a new locator on the result.  The build and the locate calls work in batches of the locate_batch knob (2^20
+   sequences / hits, at most 2^28): device memory beyond the index and the table is that of one batch. */
+typedef struct bwtm_locator bwtm_locator;
+int bwtm_locator_create(const bwtm_index* index, uint64_t max_len, bwtm_locator** out);
+void bwtm_locator_free(bwtm_locator* locator);
+uint64_t bwtm_locator_bytes(const bwtm_locator* locator);          /* device bytes of the table */
+/* (out_ids[k], out_offsets[k]) of positions[k]; a position >= bases is BWTM_EINVAL and bwtm_last_error() names it. */
+int bwtm_locate_batch(const bwtm_locator* locator, const uint64_t* positions, uint64_t count,
+                      uint64_t* out_ids, uint64_t* out_offsets);
+/* The positions of `count` closed ranges [sp, ep] in bwtm_find_batch's convention (sp > ep: empty; ep >= bases in a
+   non-empty range is BWTM_EINVAL).  max_hits > 0 keeps the first max_hits positions of every range.  hit_offsets[count + 1]
+   always receives the exclusive prefix sums of the kept hit counts.  out_ids == NULL or capacity == 0: sizes only, no GPU
+   work.  Otherwise capacity >= hit_offsets[count] (BWTM_EINVAL if not) and the hits of range r occupy
+   [hit_offsets[r], hit_offsets[r + 1]) of out_ids / out_offsets in ascending BWT position; nothing behind
+   hit_offsets[count] is touched.  The positions are generated on the device. */
+int bwtm_locate_ranges(const bwtm_locator* locator, const uint64_t* sp, const uint64_t* ep, uint64_t count,
+                       uint64_t max_hits, uint64_t* hit_offsets /* count + 1 */,
+                       uint64_t* out_ids, uint64_t* out_offsets, uint64_t capacity);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
