@@ -820,6 +820,11 @@ extern "C" int bwtm_find_batch(const bwtm_index* x, const uint8_t* patterns, con
   WHOLE_INDEX(x, "bwtm_find_batch");
   ENTER(x->ctx);
   if(count == 0) { return BWTM_OK; }
+  // the device text holds offsets[count] bytes: every pattern must lie inside it, or k_find_batch reads text[] outside its buffer
+  for(u64 k = 0; k < count; k++)
+  {
+    if(offsets[k] > offsets[k + 1]) { return fail(BWTM_EINVAL, "bwtm_find_batch: offsets must not decrease (pattern %llu)", (unsigned long long)k); }
+  }
   u64 total = offsets[count];
   if(total > 0 && !patterns) { return fail(BWTM_EINVAL, "bwtm_find_batch: null pattern text"); }
   DevBuf dt, doff, dsp, dep;
@@ -838,7 +843,7 @@ extern "C" int bwtm_extract(const bwtm_index* x, uint64_t first, uint64_t count,
   if(!x || !out) { return fail(BWTM_EINVAL, "bwtm_extract: null argument"); }
   WHOLE_INDEX(x, "bwtm_extract");
   ENTER(x->ctx);
-  if(first + count > x->n) { return fail(BWTM_EINVAL, "bwtm_extract: range past the end"); }   // bwt.h:137
+  if(first > x->n || count > x->n - first) { return fail(BWTM_EINVAL, "bwtm_extract: range past the end"); }   // bwt.h:137
   if(count == 0) { return BWTM_OK; }
   // one thread per position, and a HIP grid holds fewer than 2^32 threads: pieces of 2^30 positions (round 5: a single launch over 5.05 * 10^9
   // positions returned zeros behind the first 2^32 -- tools/scale_cli.sh wrote config 2's inputs that way and merged endmarkers)

@@ -152,10 +152,12 @@ int bwtm_inverse_select_batch(const bwtm_index* index, const uint64_t* positions
                               uint64_t* out_ranks, uint8_t* out_comps);
 /* Backward search of `count` patterns (FMI::find, fmi.h:195-209; what bwt_merge -v runs, bwt_merge.cpp:240-260).
    Pattern k is the comp values patterns[offsets[k] .. offsets[k + 1]); results are closed ranges
-   [sp, ep], empty when sp > ep; the empty pattern matches [0, bases - 1]. */
+   [sp, ep], empty when sp > ep; the empty pattern matches [0, bases - 1].  offsets[0 .. count] must not decrease
+   (BWTM_EINVAL names the first pattern whose end lies before its begin); patterns holds offsets[count] bytes. */
 int bwtm_find_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
                     uint64_t* out_sp, uint64_t* out_ep);
-/* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each. */
+/* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each.  first <= bases and
+   count <= bases - first, or BWTM_EINVAL (a sum that wraps included); first == bases with count == 0 is accepted. */
 int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_t* out);
 /* Sequences of the collection by id, as plain comp values 1..5 in forward order, endmarkers not included.
    ids == NULL: the ids first_id .. first_id + count - 1; otherwise ids[0 .. count) in any order, repeats allowed (first_id ignored).

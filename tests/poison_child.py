@@ -262,8 +262,33 @@ def family_ingest(pkg, orc):
         pkg.tune("ingest_verify", 0)
 
 
+def family_exact_builders(pkg, orc):
+    """Every single-index builder on every small stream whose size is on a record, group, chunk or segment edge (tests/boundary_inputs.py):
+    a last record, a last chunk or a last super row that nobody wrote holds the poison, not a zero."""
+    import boundary_inputs as bi
+    from test_gpu_exact_sizes import BUILDERS, check_small_builder
+    for kind, n in bi.SMALL_STREAMS:
+        for builder in BUILDERS:
+            check_small_builder(pkg, orc, kind, n, builder)
+
+
+def family_exact_merges(pkg, orc):
+    """Every form of the merge at every exact n_out under both dispatches of the search, the consumers included."""
+    import boundary_inputs as bi
+    from test_gpu_exact_sizes import FORMS, PairCase, check_input_consumers, check_merge_form
+    for name in bi.READ_PAIRS:
+        case = PairCase(pkg, orc, name)
+        for form in FORMS:
+            for algo in (1, 2):
+                check_merge_form(pkg, orc, case, form, algo, consumers=(algo == 2))
+        check_input_consumers(pkg, case)
+        case.free()
+        pkg.trim()
+
+
 FAMILIES = {"reads": family_reads, "odd": family_odd, "runs": family_runs, "encoder": family_encoder, "epochs": family_epochs, "host": family_host,
-            "slices": family_slices, "parts": family_parts, "ingest": family_ingest}
+            "slices": family_slices, "parts": family_parts, "ingest": family_ingest, "exact_builders": family_exact_builders,
+            "exact_merges": family_exact_merges}
 
 
 def main(family):

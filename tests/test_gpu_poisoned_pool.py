@@ -44,6 +44,15 @@ def test_parity_on_poisoned_memory(bwtm, family, word, pool):
     assert fills > 0 and nbytes >= 256 * fills, (fills, nbytes)
 
 
+@pytest.mark.parametrize("word", ["0x00000000", "0xA5A5A5A5"])
+@pytest.mark.parametrize("family", ["exact_builders", "exact_merges"])
+def test_exact_sizes_on_poisoned_memory(bwtm, family, word):
+    """The small builder and merge cases of tests/test_gpu_exact_sizes.py once more on poisoned memory: at sizes that are a multiple of a
+    record, a chunk or a segment, the last unit holds no position and is the one nobody may have written."""
+    fills, nbytes = run_child(family, dict(BWTM_POOL_POISON=word))
+    assert fills > 0 and nbytes >= 256 * fills, (fills, nbytes)
+
+
 def test_poison_mode_is_off_by_default_and_counted_when_on(bwtm):
     """The proof of activity proves something: without the variable (or with a misspelt one) the child reports no fill at all."""
     env = {k: v for k, v in os.environ.items() if k != "BWTM_POOL_POISON"}

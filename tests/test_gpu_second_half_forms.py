@@ -73,13 +73,15 @@ def narrowest_width(longest_block):
     return 1 if longest_block < 0xFF else 2 if longest_block < 0xFFFF else 4
 
 
-def check_index_by_probes(ix, m, sym, rng):
+def check_index_by_probes(ix, m, sym, rng, extra=(), nq=4000):
     """check_index for an index too large for a table of all counts: the symbols, then rank of every symbol, clamping and
-    inverse_select at random positions, around every cut of 65 536 positions and around 2^25, against the oracle's own rank."""
+    inverse_select at nq random positions, around every cut of 65 536 positions and around 2^25, and at the caller's `extra` positions
+    (those outside 0 .. n are dropped), against the oracle's own rank."""
     n = sym.size
     assert ix.bases == n and np.array_equal(ix.extract(0, n), sym)
     cuts = np.arange(shi.SEGMENT, n, shi.SEGMENT, dtype=np.int64)
-    pos = np.concatenate([rng.integers(0, n + 1, 4000), cuts - 1, cuts, cuts + 1, [(1 << 25) - 1, 1 << 25, (1 << 25) + 1], [0, n, n - 1, 127, 128, 129]])
+    pos = np.concatenate([rng.integers(0, n + 1, nq), cuts - 1, cuts, cuts + 1, [(1 << 25) - 1, 1 << 25, (1 << 25) + 1], [0, n, n - 1, 127, 128, 129],
+                          np.asarray(extra, dtype=np.int64)])
     pos = np.unique(pos[(pos >= 0) & (pos <= n)]).astype(np.uint64)
     for c in range(6):
         got = ix.rank(pos, np.full(pos.size, c, dtype=np.uint8))
