@@ -143,6 +143,8 @@ SYMBOLS = [
     ("bwtm_locator_bytes", u64, [vp]),
     ("bwtm_locate_batch", C.c_int, [vp, p_u64, u64, p_u64, p_u64]),
     ("bwtm_locate_ranges", C.c_int, [vp, p_u64, p_u64, u64, u64, p_u64, p_u64, p_u64, u64]),
+    ("bwtm_overlap_batch", C.c_int, [vp, p_u8, p_u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
+    ("bwtm_overlap_sequences", C.c_int, [vp, p_u64, u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -839,6 +841,65 @@ class Locator:
         (hit_offsets, ids, offsets); pattern k occurs at offset offsets[h] of sequence ids[h] for h in [hit_offsets[k], hit_offsets[k + 1])."""
         sp, ep = self.index.find(patterns)
         return self.locate_ranges(sp, ep, max_hits)
+
+    def _overlap_calls(self, call, count, max_hits):
+        """The sizing call, then the real one: call(hit_offsets, ids, lengths, capacity) is one of the two C calls with its queries bound."""
+        hit_offsets = np.zeros(int(count) + 1, dtype=np.uint64)
+        check(call(hit_offsets.ctypes.data_as(p_u64), None, None, 0))
+        total = int(hit_offsets[-1])
+        ids = np.zeros(total, dtype=np.uint64)
+        lengths = np.zeros(total, dtype=np.uint64)
+        if total > 0:
+            check(call(hit_offsets.ctypes.data_as(p_u64), ids.ctypes.data_as(p_u64), lengths.ctypes.data_as(p_u64), total))
+        return hit_offsets, ids, lengths
+
+    def overlaps(self, ids=None, first=0, count=None, min_overlap=1, max_hits=0, skip_self=False):
+        """Suffix-prefix overlaps of sequences of the index (bwtm_overlap_sequences): the queries are ids (any order, repeats allowed), or
+        first .. first + count - 1 (count=None: up to the last sequence).  Returns (hit_offsets [count + 1], ids, lengths): for h in
+        [hit_offsets[k], hit_offsets[k + 1]), the first lengths[h] symbols of sequence ids[h] are the last lengths[h] symbols of query k,
+        lengths[h] >= min_overlap; longest overlap first, then targets in BWT order.  max_hits > 0 keeps the first max_hits hits of every
+        query.  skip_self drops, on the host, the hit of a query with itself over its whole length and recomputes hit_offsets; it applies
+        AFTER the max_hits cut, so a query can keep max_hits - 1 hits."""
+        if not self.h:
+            raise BwtmError("the locator has been freed")
+        ip = None
+        if ids is not None:
+            ids, ip = _u64(ids)
+            count = ids.size
+            queries = ids
+        else:
+            if count is None:
+                count = max(self.index.sequences - int(first), 0)
+            queries = np.arange(int(first), int(first) + int(count), dtype=np.uint64)
+        count = int(count)
+        hit_offsets, targets, lengths = self._overlap_calls(
+            lambda ho, oi, ol, cap: lib().bwtm_overlap_sequences(self.h, ip, int(first), count, int(min_overlap), int(max_hits), ho, oi, ol, cap), count, max_hits)
+        if skip_self and targets.size > 0:
+            per_query = np.diff(hit_offsets).astype(np.int64)
+            owner = np.repeat(np.arange(count), per_query)
+            # a query that has hits at all hits itself over its whole length L, and no hit is longer: the first hit of a query has length L
+            full = lengths[hit_offsets[:-1].astype(np.int64)[owner]]
+            drop = (targets == queries[owner]) & (lengths == full)
+            keep = ~drop
+            kept_per_query = np.bincount(owner[keep], minlength=count).astype(np.uint64)
+            hit_offsets = np.zeros(count + 1, dtype=np.uint64)
+            hit_offsets[1:] = np.cumsum(kept_per_query)
+            targets, lengths = targets[keep], lengths[keep]
+        return hit_offsets, targets, lengths
+
+    def overlap_patterns(self, patterns, min_overlap, max_hits=0):
+        """Suffix-prefix overlaps of patterns that need not be sequences of the index (bwtm_overlap_batch): (hit_offsets, ids, lengths) as in
+        overlaps(); a pattern holds comp values 1..5 and may be longer than every sequence."""
+        if not self.h:
+            raise BwtmError("the locator has been freed")
+        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lens)
+        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+        text, tp = _u8(text)
+        return self._overlap_calls(
+            lambda ho, oi, ol, cap: lib().bwtm_overlap_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_overlap), int(max_hits), ho, oi, ol, cap),
+            len(patterns), max_hits)
 
 
 class RankArray:

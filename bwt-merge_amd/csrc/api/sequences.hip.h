@@ -9,6 +9,50 @@ namespace
 constexpr u64 SEQ_MAX_LEN_DEFAULT = 1ull << 16, SEQ_MAX_LEN_LIMIT = 1ull << 24;
 // four lanes per sequence and fewer than 2^32 threads per grid (the note at LAUNCH_CFG): a batch is one launch
 constexpr u64 SEQ_BATCH_LIMIT = 1ull << 28;
+
+// The per-batch stage of reading sequences by id, shared by bwtm_sequences_extract (which brings the text to the host) and
+// bwtm_overlap_sequences (which searches it where it is): the device buffers of one batch and its two launches.
+struct SeqBatch
+{
+  DevBuf d_ids, d_len, d_off, d_status, d_text;
+  std::vector<u32> h_len;               // the batch's lengths, after lengths()
+  std::vector<u64> h_off;               // batch-local offsets (nb + 1 entries), filled by the caller between lengths() and emit()
+  bool on_host = true;                  // false: the lengths stay in d_len, and the caller leaves the nb + 1 offsets in d_off before emit()
+  int alloc(u64 batch, bool with_ids, bool with_text, bool host_side = true)
+  {
+    on_host = host_side;
+    if(with_ids) { TRY(d_ids.alloc(batch * sizeof(u64))); }
+    TRY(d_len.alloc(batch * sizeof(u32))); TRY(d_status.alloc(sizeof(u64)));
+    if(with_text) { TRY(d_off.alloc((batch + 1) * sizeof(u64))); }
+    h_len.assign(on_host ? batch : 0, 0);
+    h_off.assign(on_host && with_text ? batch + 1 : 0, 0);
+    return BWTM_OK;
+  }
+  const u64* ids_or_null(const u64* ids) const { return (ids ? d_ids.as<const u64>() : (const u64*)nullptr); }
+  // ids up (when given), k_seq_lengths, lengths down into h_len (on_host); *bad = the first sequence of the batch that failed, or SEQ_STATUS_NONE
+  int lengths(const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 max_len, u64* bad)
+  {
+    if(ids) { HIP_TRY(hipMemcpyAsync(d_ids.p, ids, nb * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
+    HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                       // SEQ_STATUS_NONE
+    LAUNCH("seq_lengths", k_seq_lengths, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), ids_or_null(ids), first_id, nb, (u32)max_len,
+      d_len.as<u32>(), d_status.as<unsigned long long>());
+    if(on_host) { HIP_TRY(hipMemcpyAsync(h_len.data(), d_len.p, nb * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
+    TRY(fetch_u64(d_status.as<u64>(), 0));
+    HIP_TRY(hipStreamSynchronize(CTX.stream));
+    *bad = CTX.host_scratch[0];
+    return BWTM_OK;
+  }
+  // the batch's text allocated at its exact size `local`, h_off up (on_host), k_seq_emit (not launched for an empty text); nothing is awaited
+  int emit(const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 local)
+  {
+    TRY(d_text.alloc(local));
+    if(on_host) { HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (nb + 1) * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
+    if(local == 0) { return BWTM_OK; }
+    LAUNCH("seq_emit", k_seq_emit, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), ids_or_null(ids), first_id, nb, d_off.as<const u64>(),
+      d_len.as<const u32>(), d_text.as<u8>());
+    return BWTM_OK;
+  }
+};
 } // namespace
 
 // Every batch of at most extract_batch sequences: ids up (when given), k_seq_lengths, lengths down, prefix sums on the host into the
@@ -40,35 +84,25 @@ extern "C" int bwtm_sequences_extract(const bwtm_index* x, const uint64_t* ids, 
   }
   const bool sizes_only = (!text || capacity == 0);
   const u64 batch = std::min<u64>(std::min<u64>((u64)g_tune.extract_batch, SEQ_BATCH_LIMIT), count);
-  DevBuf d_ids, d_len, d_off, d_status, d_text;
-  if(ids) { TRY(d_ids.alloc(batch * sizeof(u64))); }
-  TRY(d_len.alloc(batch * sizeof(u32))); TRY(d_status.alloc(sizeof(u64)));
-  if(!sizes_only) { TRY(d_off.alloc(batch * sizeof(u64))); }
-  std::vector<u32> h_len(batch);
-  std::vector<u64> h_off(sizes_only ? 0 : batch);
+  SeqBatch b;
+  TRY(b.alloc(batch, ids != nullptr, !sizes_only));
   u64 running = 0;
   for(u64 done = 0; done < count; done += batch)
   {
     const u64 nb = std::min(batch, count - done);
-    const u64 grid = div_up(4 * nb, BLOCK_THREADS);
-    if(ids) { HIP_TRY(hipMemcpyAsync(d_ids.p, ids + done, nb * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                       // SEQ_STATUS_NONE
-    LAUNCH("seq_lengths", k_seq_lengths, grid, BLOCK_THREADS, x->view(), (ids ? d_ids.as<const u64>() : (const u64*)nullptr), first_id + done, nb, (u32)max_len,
-      d_len.as<u32>(), d_status.as<unsigned long long>());
-    HIP_TRY(hipMemcpyAsync(h_len.data(), d_len.p, nb * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream));
-    TRY(fetch_u64(d_status.as<u64>(), 0));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    if(CTX.host_scratch[0] != SEQ_STATUS_NONE)
+    u64 bad = 0;
+    TRY(b.lengths(x, (ids ? ids + done : nullptr), first_id + done, nb, max_len, &bad));
+    if(bad != SEQ_STATUS_NONE)
     {
-      const u64 bad = done + CTX.host_scratch[0];
+      bad += done;
       return fail(BWTM_EINVAL, "bwtm_sequences_extract: sequence %llu is longer than max_len = %llu (or the index is damaged)",
         (unsigned long long)(ids ? ids[bad] : first_id + bad), (unsigned long long)max_len);
     }
     u64 local = 0;
     for(u64 k = 0; k < nb; k++)
     {
-      if(!sizes_only) { h_off[k] = local; }
-      local += h_len[k];
+      if(!sizes_only) { b.h_off[k] = local; }
+      local += b.h_len[k];
       offsets[done + k + 1] = running + local;
     }
     if(!sizes_only && local > 0)
@@ -78,11 +112,9 @@ extern "C" int bwtm_sequences_extract(const bwtm_index* x, const uint64_t* ids, 
         return fail(BWTM_EINVAL, "bwtm_sequences_extract: capacity %llu is too small (the first %llu sequences take %llu bytes)", (unsigned long long)capacity,
           (unsigned long long)(done + nb), (unsigned long long)(running + local));
       }
-      TRY(d_text.alloc(local));
-      HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), nb * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-      LAUNCH("seq_emit", k_seq_emit, grid, BLOCK_THREADS, x->view(), (ids ? d_ids.as<const u64>() : (const u64*)nullptr), first_id + done, nb, d_off.as<const u64>(),
-        d_len.as<const u32>(), d_text.as<u8>());
-      HIP_TRY(hipMemcpyAsync(text + running, d_text.p, local, hipMemcpyDeviceToHost, CTX.stream));
+      b.h_off[nb] = local;
+      TRY(b.emit(x, (ids ? ids + done : nullptr), first_id + done, nb, local));
+      HIP_TRY(hipMemcpyAsync(text + running, b.d_text.p, local, hipMemcpyDeviceToHost, CTX.stream));
       HIP_TRY(hipStreamSynchronize(CTX.stream));                                              // the batch's buffers are reused
     }
     running += local;

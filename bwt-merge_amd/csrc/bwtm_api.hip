@@ -55,3 +55,4 @@ using namespace bwtm;
 #include "api/ingest.hip.h"
 #include "api/sequences.hip.h"
 #include "api/locate.hip.h"
+#include "api/overlap.hip.h"

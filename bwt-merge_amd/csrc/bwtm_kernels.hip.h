@@ -35,6 +35,10 @@
     k_locate_build, k_locate_check, k_locate
                        from a BWT position to (sequence id, offset): the same walk from any position, and one table per index that
                        numbers the whole-sequence suffixes (kernels/locate.hip.h; the step the reference's queries leave to the host)
+    k_overlap_scan<EMIT>, k_overlap_expand
+                       suffix-prefix overlaps: one backward search per query whose rank(., 0) pairs are intervals of the locator's
+                       table, counted, then emitted longest first and expanded to (id, length) (kernels/overlap.hip.h; the overlap
+                       step of a string-graph assembler, no counterpart in the reference)
 */
 #pragma once
 
@@ -83,6 +87,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/search_walk.hip.h"
 #include "kernels/sequences.hip.h"
 #include "kernels/locate.hip.h"
+#include "kernels/overlap.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

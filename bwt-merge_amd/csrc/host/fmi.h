@@ -209,6 +209,26 @@ public:
     for(size_type h = 0; h < total; h++) { hits[h] = hit_type(ids[h], offsets[h]); }
   }
 
+  typedef std::pair<size_type, size_type> overlap_type;             // (target sequence, length of the overlap)
+
+  // Suffix-prefix overlaps of the sequences ids.first .. ids.second with the collection (bwtm_overlap_sequences: a sizing call, then the real
+  // one): those of the k-th query are hits[hit_offsets[k] .. hit_offsets[k + 1]), the first `length` symbols of `target` being the last
+  // `length` symbols of the query, length >= min_overlap; longest first, then targets in BWT order.  A query's hit with itself over its
+  // whole length is among them.  max_hits > 0 keeps the first max_hits hits of every query.
+  void overlaps(range_type ids, size_type min_overlap, std::vector<size_type>& hit_offsets, std::vector<overlap_type>& hits, size_type max_hits = 0) const
+  {
+    const size_type count = (Range::empty(ids) ? 0 : Range::length(ids));
+    hit_offsets.assign(count + 1, 0); hits.clear();
+    if(count == 0) { return; }
+    gpuCheck(bwtm_overlap_sequences(this->handle, nullptr, ids.first, count, min_overlap, max_hits, hit_offsets.data(), nullptr, nullptr, 0), "Locator::overlaps()");
+    const size_type total = hit_offsets[count];
+    if(total == 0) { return; }
+    std::vector<uint64_t> targets(total), lengths(total);
+    gpuCheck(bwtm_overlap_sequences(this->handle, nullptr, ids.first, count, min_overlap, max_hits, hit_offsets.data(), targets.data(), lengths.data(), total), "Locator::overlaps()");
+    hits.resize(total);
+    for(size_type h = 0; h < total; h++) { hits[h] = overlap_type(targets[h], lengths[h]); }
+  }
+
 private:
   bwtm_locator* handle = nullptr;
 };

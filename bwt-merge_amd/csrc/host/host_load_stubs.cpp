@@ -27,5 +27,7 @@ void bwtm_locator_free(bwtm_locator*) {}
 uint64_t bwtm_locator_bytes(const bwtm_locator*) { return 0; }
 int bwtm_locate_batch(const bwtm_locator*, const uint64_t*, uint64_t, uint64_t*, uint64_t*) { return BWTM_ENODEV; }
 int bwtm_locate_ranges(const bwtm_locator*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
+int bwtm_overlap_batch(const bwtm_locator*, const uint8_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
+int bwtm_overlap_sequences(const bwtm_locator*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
 
 }

@@ -1,8 +1,9 @@
 /*
   kernels/diagnostics.hip.h -- timing-only and A/B variants of the search kernels.  NOT part of the product build:
   compiled only with -DBWTM_DIAGNOSTICS (tools/build_variant.sh), selected through the bwtm_tune() keys walk_emit,
-  walk_ablate, walk_kernel, walk_variant, scatter_kernel, walk_blocks.  Some of them produce results that are not a
-  rank array (see the comments); DESIGN.md section 3.1 records what was measured with them.
+  walk_ablate, walk_kernel, walk_variant, scatter_kernel, walk_blocks, and an exact A/B partner of the overlap search
+  (overlap_kernel).  Some of them produce results that are not a rank array (see the comments); DESIGN.md sections 3.1 and
+  3.9 record what was measured with them.
   Part of bwtm_kernels.hip.h (included there, inside namespace bwtm); gfx950 only.
 */
 #pragma once
@@ -222,5 +223,76 @@ __global__ void __launch_bounds__(WL_THREADS, 4) k_lf_walk_lds(IndexView A, Inde
       __syncthreads();
       if(!any) { break; }
     }
+  }
+}
+
+//------------------------------------------------------------------------------
+// k_overlap_scan (kernels/overlap.hip.h) in k_find_batch's shape: ONE lane per query, index_ranks twice per step (each lane loads both whole
+// records with four dwordx4 each).  The same search, the same counts and records -- an exact A/B partner of the quad form, selected with
+// bwtm_tune("overlap_kernel", 1); DESIGN.md section 3.9 records what was measured (tools/overlap_bench.py --kernel 1).
+template<bool EMIT>
+__global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_scan_lane(IndexView x, const u8* text, const u64* offsets, u64 count, u64 min_overlap, u64 max_hits,
+  u64* rec_base, u64* n_hits, u64* hit_base, OverlapRecs recs)
+{
+  __shared__ u64 sC[8];
+  if(threadIdx.x < 8) { sC[threadIdx.x] = x.C[threadIdx.x]; }
+  __syncthreads();
+  const u64 k = (u64)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+  if(k >= count) { return; }
+  const u64 begin = offsets[k], end = offsets[k + 1];
+  u64 total = 0, kept = 0, nint = 0, base_r = 0, base_h = 0;
+  if(EMIT)
+  {
+    total = n_hits[k]; base_r = rec_base[k]; nint = rec_base[k + 1] - base_r; base_h = hit_base[k];
+    kept = (max_hits > 0 && total > max_hits ? max_hits : total);
+  }
+  u64 seen = 0, found = 0;
+  if(end > begin)
+  {
+    u64 pos = end - 1, len = 1;
+    const u32 c0 = text[pos];
+    u64 sp = 0, e1 = 0;
+    if(c0 >= 1 && c0 <= 5) { sp = sC[c0]; e1 = sC[c0 + 1]; }
+    while(sp < e1 && e1 <= x.n)
+    {
+      const bool at_end = (e1 == x.n);
+      const u32 c = (pos > begin ? (u32)text[pos - 1] : 0u);
+      u64 rs[6], re[6];
+      index_ranks(x, sp, rs); index_ranks(x, (at_end ? e1 - 1 : e1), re);
+      if(at_end)
+      {
+#pragma unroll
+        for(u32 s = 1; s < 6; s++) { re[s] = sC[s + 1] - sC[s]; }              // rank(n, .) from C
+      }
+      if(len >= min_overlap)
+      {
+        const u64 z0 = sp - (rs[1] + rs[2] + rs[3] + rs[4] + rs[5]), z1 = e1 - (re[1] + re[2] + re[3] + re[4] + re[5]);
+        if(z1 > z0)
+        {
+          const u64 cnt = z1 - z0;
+          if(EMIT)
+          {
+            if(found >= nint || cnt > total - seen) { break; }
+            const u64 lo = total - seen - cnt;
+            const u64 r = base_r + (nint - 1 - found);
+            recs.first[r] = base_h + (lo < kept ? lo : kept);
+            recs.z0[r] = z0;
+            recs.cnt[r] = (lo < kept ? (cnt < kept - lo ? cnt : kept - lo) : 0);
+            recs.len[r] = len;
+          }
+          seen += cnt; found++;
+        }
+      }
+      if(c < 1 || c > 5) { break; }
+      const u64 a = (c == 1 ? rs[1] : (c == 2 ? rs[2] : (c == 3 ? rs[3] : (c == 4 ? rs[4] : rs[5]))));
+      const u64 b = (c == 1 ? re[1] : (c == 2 ? re[2] : (c == 3 ? re[3] : (c == 4 ? re[4] : re[5]))));
+      sp = sC[c] + a; e1 = sC[c] + b;
+      pos--; len++;
+    }
+  }
+  if(!EMIT)
+  {
+    rec_base[k] = found; n_hits[k] = seen; hit_base[k] = (max_hits > 0 && seen > max_hits ? max_hits : seen);
+    if(k + 1 == count) { rec_base[count] = 0; hit_base[count] = 0; }
   }
 }

@@ -197,6 +197,34 @@ int bwtm_locate_ranges(const bwtm_locator* locator, const uint64_t* sp, const ui
                        uint64_t max_hits, uint64_t* hit_offsets /* count + 1 */,
                        uint64_t* out_ids, uint64_t* out_offsets, uint64_t capacity);
 
+/* Suffix-prefix overlaps, the overlap step of a string-graph assembler: a hit of a query Q of L symbols is a pair (t, l) with
+   min_overlap <= l <= L, l <= |S_t| and S_t[0 .. l) == Q[L - l .. L).  l == |S_t| is a hit (S_t is a suffix of Q), and when Q is
+   sequence q of the index, (q, L) is one too; a sequence that overlaps itself with l < L is an ordinary hit.  Reverse complements
+   are not searched: an index that holds both strands gives them.  The hits of a query come longest overlap first and, within one
+   length, in ascending BWT position of the target's whole-sequence suffix (targets ascending as strings, a prefix before its
+   extensions, equal ones by id).  max_hits > 0 keeps the first max_hits hits of every query in that order: the longest.
+   One backward search per query and one table entry per hit: no walk.
+   hit_offsets[count + 1] always receives the exclusive prefix sums of the kept hit counts.  out_ids == NULL or capacity == 0:
+   sizes only -- unlike bwtm_locate_ranges, that call does run the search (its count pass) on the GPU.  Otherwise
+   capacity >= hit_offsets[count] (BWTM_EINVAL if not, and nothing beyond hit_offsets is written) and the hits of query k occupy
+   [hit_offsets[k], hit_offsets[k + 1]) of out_ids (the target t) / out_lengths (l); nothing behind hit_offsets[count] is touched.
+   BWTM_EINVAL, with bwtm_last_error() naming the first offender: min_overlap == 0, a query symbol outside 1..5, offsets that
+   decrease, an id >= sequences, a sequence longer than the locator's max_len, an entry of the table that is no sequence.  A query
+   shorter than min_overlap has no hits; a pattern may be longer than every sequence.  The calls work in batches of the
+   overlap_batch knob (2^20 queries, at most 2^28) and expand in hit batches of locate_batch: device memory beyond the index and
+   the table is one batch's text, 24 bytes per query, its interval records (32 bytes each, at most one per symbol of the text) and one
+   batch of hits.
+   A call of more than one batch runs the count pass of every batch twice (once for the sizes, once before its expansion). */
+/* queries as patterns: query k = queries[offsets[k] .. offsets[k+1]), comp values 1..5 */
+int bwtm_overlap_batch(const bwtm_locator* locator, const uint8_t* queries, const uint64_t* offsets, uint64_t count,
+                       uint64_t min_overlap, uint64_t max_hits, uint64_t* hit_offsets /* count + 1 */,
+                       uint64_t* out_ids, uint64_t* out_lengths, uint64_t capacity);
+/* queries are sequences of the index itself, read on the device and never brought to the host: ids == NULL: first_id ..
+   first_id + count - 1, otherwise ids[0 .. count) in any order, repeats allowed (the conventions of bwtm_sequences_extract) */
+int bwtm_overlap_sequences(const bwtm_locator* locator, const uint64_t* ids, uint64_t first_id, uint64_t count,
+                           uint64_t min_overlap, uint64_t max_hits, uint64_t* hit_offsets,
+                           uint64_t* out_ids, uint64_t* out_lengths, uint64_t capacity);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
