@@ -1,6 +1,6 @@
 /*
-  api/index.hip.h -- the device index: BWT::load + BWT::build (pipelined upload, transcode), the canonical
-  encoder with the pipelined download, samples, batch queries.  Part of bwtm_api.hip.
+  api/index.hip.h -- the device index: BWT::load + BWT::build (pipelined upload, transcode), the canonical encoder (EncodePasses, the
+  one driver of its kernels, also for api/slices.hip.h) with the pipelined download, samples, batch queries.  Part of bwtm_api.hip.
 */
 #pragma once
 
@@ -374,38 +374,89 @@ int ensure_view(const bwtm_index* x)
 
 //------------------------------------------------------------------------------
 // Encoder: records -> native bytes (RunBuffer + Run::write) + block starts (BWT::build).
+//
+// EncodePasses is the one driver of the seven kernels (kernels/encoder.hip.h): its passes over the segments [seg_first, seg_end) of a record
+// array, in call order, and the size tables they leave for each other.  The whole index (encode_size / encode_emit) and an output-range slice
+// (api/slices.hip.h) differ in three numbers: the first segment, the head carried in from the slices before and the byte offset of the start.
+struct EncodePasses
+{
+  const uint4* recs = nullptr;         // addressed by the global record number (a slice: bwtm_slice::recs_virtual)
+  u64 nrecs = 0, n = 0;                // of the whole index
+  u64 seg_first = 0, seg_end = 0;
+  DevBuf lasthead, table, group_table, group_base, seg_base;
+  u64 ngroups = 0, head_carry = 0;
+
+  u64 nseg() const { return seg_end - seg_first; }
+  u64 ntiles() const { return (n >> 6) + 1; }
+  u64 bytes() const { return lasthead.bytes + table.bytes + group_table.bytes + group_base.bytes + seg_base.bytes; }
+  void release() { lasthead.release(); table.release(); group_table.release(); group_base.release(); seg_base.release(); }
+
+  // lasthead[k] = (last head of the range before its segment k) + 1.  own_last: one more entry, the range's own last head (a slice hands it on).
+  int heads(bool own_last)
+  {
+    const u64 entries = nseg() + (own_last ? 1 : 0);
+    TRY(lasthead.alloc(entries * sizeof(u64)));
+    if(own_last) { HIP_TRY(hipMemsetAsync(lasthead.as<u64>() + nseg(), 0, sizeof(u64), CTX.stream)); }
+    LAUNCH("enc_lasthead", k_enc_lasthead, div_up(nseg() * WAVE, BLOCK_THREADS), BLOCK_THREADS, recs, nrecs, n, ntiles(), seg_first, seg_end, lasthead.as<u64>() - seg_first);
+    TRY(device_scan<1>(lasthead.as<u64>(), lasthead.as<u64>(), entries));             // exclusive max-scan
+    return BWTM_OK;
+  }
+
+  // Every segment's bytes as a function of its start offset mod 64, folded per group of segments.  carry: the last head before the range, + 1.
+  int sizes(u64 carry)
+  {
+    head_carry = carry;
+    ngroups = div_up(nseg(), FOLD_GROUP);
+    TRY(table.alloc(nseg() * 64 * sizeof(u32)));
+    TRY(group_table.alloc(ngroups * 64 * sizeof(u64)));
+    LAUNCH("enc_size", k_enc_size, div_up(nseg() * WAVE, BLOCK_THREADS), BLOCK_THREADS, recs, nrecs, n, ntiles(), seg_first, seg_end,
+      lasthead.as<const u64>() - seg_first, head_carry, table.as<u32>() - seg_first * 64);
+    LAUNCH("fold_group", k_fold_group, ngroups, WAVE, table.as<const u32>(), nseg(), group_table.as<u64>());
+    return BWTM_OK;
+  }
+
+  // The byte offset of every group and segment of a range that starts at byte_offset; group_base[ngroups] is where it ends.
+  int place(u64 byte_offset)
+  {
+    TRY(group_base.alloc((ngroups + 1) * sizeof(u64)));
+    TRY(seg_base.alloc(nseg() * sizeof(u64)));
+    LAUNCH("fold_top", k_fold_top, 1, WAVE, group_table.as<const u64>(), ngroups, byte_offset, group_base.as<u64>());
+    LAUNCH("fold_seg", k_fold_seg, ngroups, WAVE, table.as<const u32>(), nseg(), group_base.as<const u64>(), seg_base.as<u64>());
+    return BWTM_OK;
+  }
+
+  // Writes the segments [s0, s1) of the range.  out, block_start and cum32 are addressed by the GLOBAL byte / block number (a slice passes shifted
+  // pointers).  cum32 null: no samples; sup set: the slice form of the samples, which needs the slice's first position and the symbol before it.
+  int emit(u64 s0, u64 s1, u8* out, u64* block_start, u32* cum32, u64 cum_stride, u64 slice_start = 0, u32 halo_symbol = 0, const u64* sup = nullptr)
+  {
+#define ENC_EMIT(...) LAUNCH("enc_emit", (k_enc_emit<__VA_ARGS__>), div_up((s1 - s0) * WAVE, BLOCK_THREADS), BLOCK_THREADS, recs, nrecs, n, ntiles(), s0, s1, \
+    lasthead.as<const u64>() - seg_first, head_carry, seg_base.as<const u64>() - seg_first, out, block_start, cum32, cum_stride, slice_start, halo_symbol, sup)
+    if(!cum32) { ENC_EMIT(false); } else if(!sup) { ENC_EMIT(true); } else { ENC_EMIT(true, true); }
+#undef ENC_EMIT
+    return BWTM_OK;
+  }
+};
 
 struct EncodePlan
 {
-  u64 ntiles = 0, nseg = 0, ngroups = 0, total = 0;
-  DevBuf lasthead, table, group_table, group_base, seg_base;
+  EncodePasses enc;
+  u64 total = 0;
   std::vector<u64> group_base_host;       // byte offset at which every fold group of segments starts (+ total)
 };
 
 // Size pass: the byte offset of every segment (and with it the size of the stream).  Synchronises.
 int encode_size(bwtm_index* x, EncodePlan& plan)
 {
-  plan.ntiles = (x->n >> 6) + 1;
-  plan.nseg = div_up(plan.ntiles, SEG_TILES);
-  plan.ngroups = div_up(plan.nseg, FOLD_GROUP);
-  const u64 nseg = plan.nseg, ngroups = plan.ngroups;
-  TRY(plan.lasthead.alloc(nseg * sizeof(u64)));
-  TRY(plan.table.alloc(nseg * 64 * sizeof(u32)));
-  TRY(plan.group_table.alloc(ngroups * 64 * sizeof(u64)));
-  TRY(plan.group_base.alloc((ngroups + 1) * sizeof(u64)));
-  TRY(plan.seg_base.alloc(nseg * sizeof(u64)));
-  const u64 wave_grid = div_up(nseg * WAVE, BLOCK_THREADS);
-  LAUNCH("enc_lasthead", k_enc_lasthead, wave_grid, BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, (u64)0, nseg, plan.lasthead.as<u64>());
-  TRY(device_scan<1>(plan.lasthead.as<u64>(), plan.lasthead.as<u64>(), nseg));       // -> (last head before the segment) + 1
-  LAUNCH("enc_size", k_enc_size, wave_grid, BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, (u64)0, nseg,
-    plan.lasthead.as<const u64>(), (u64)0, plan.table.as<u32>());
-  LAUNCH("fold_group", k_fold_group, ngroups, WAVE, plan.table.as<const u32>(), nseg, plan.group_table.as<u64>());
-  LAUNCH("fold_top", k_fold_top, 1, WAVE, plan.group_table.as<const u64>(), ngroups, (u64)0, plan.group_base.as<u64>());
-  LAUNCH("fold_seg", k_fold_seg, ngroups, WAVE, plan.table.as<const u32>(), nseg, plan.group_base.as<const u64>(), plan.seg_base.as<u64>());
-  plan.group_base_host.resize(ngroups + 1);
-  HIP_TRY(hipMemcpyAsync(plan.group_base_host.data(), plan.group_base.p, (ngroups + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+  EncodePasses& enc = plan.enc;
+  enc.recs = x->recs.as<const uint4>(); enc.nrecs = x->nrecs; enc.n = x->n;
+  enc.seg_first = 0; enc.seg_end = div_up(enc.ntiles(), SEG_TILES);
+  TRY(enc.heads(false));
+  TRY(enc.sizes(0));
+  TRY(enc.place(0));
+  plan.group_base_host.resize(enc.ngroups + 1);
+  HIP_TRY(hipMemcpyAsync(plan.group_base_host.data(), enc.group_base.p, (enc.ngroups + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
   HIP_TRY(hipStreamSynchronize(CTX.stream));
-  plan.total = plan.group_base_host[ngroups];
+  plan.total = plan.group_base_host[enc.ngroups];
   return BWTM_OK;
 }
 
@@ -413,43 +464,26 @@ int encode_size(bwtm_index* x, EncodePlan& plan)
 // while the next range is being written (the caller joins the copy stream).
 int encode_emit(bwtm_index* x, EncodePlan& plan, u8* host_out, bool with_cum = false)
 {
-  const u64 total = plan.total;
-  x->nbytes = total;
-  x->nblocks = div_up(total, RLE_BLOCK);
-  TRY(alloc_native(x->data, total));
+  x->nbytes = plan.total;
+  x->nblocks = div_up(plan.total, RLE_BLOCK);
+  TRY(alloc_native(x->data, plan.total));
   x->gcum.release(); x->ngroups = 0; x->cum32.release();
-  const u64 cum_stride = x->nblocks + 1;
-  if(with_cum) { TRY(x->cum32.alloc(cum32_bytes(x->nblocks))); }
+  const u64 cum_stride = (with_cum ? x->nblocks + 1 : 0);
+  if(with_cum) { TRY(x->cum32.alloc(cum32_bytes(x->nblocks))); }                     // else null: the encoder writes no samples
   // k_enc_emit records the position at which every 64-byte block starts; the entry after the last block is n
   TRY(x->block_start.alloc((x->nblocks + 1) * sizeof(u64)));
   CTX.host_scratch[63] = x->n;
   HIP_TRY(hipMemcpyAsync(x->block_start.as<u64>() + x->nblocks, CTX.host_scratch + 63, sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
+  EncodePasses& enc = plan.enc;
   hipEvent_t ev = nullptr;
   if(host_out) { HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
   int rc = BWTM_OK;
-  for(u64 g0 = 0; g0 < plan.ngroups && rc == BWTM_OK; )
+  for(u64 g0 = 0; g0 < enc.ngroups && rc == BWTM_OK; )
   {
     u64 g1 = g0 + 1;
-    if(host_out) { while(g1 < plan.ngroups && plan.group_base_host[g1] - plan.group_base_host[g0] < (u64)g_tune.download_chunk) { g1++; } }
-    else { g1 = plan.ngroups; }
-    const u64 s0 = g0 * FOLD_GROUP, s1 = std::min(plan.nseg, g1 * FOLD_GROUP);
-    auto launch = [&]() -> int
-    {
-      if(with_cum)
-      {
-        LAUNCH("enc_emit", k_enc_emit<true>, div_up((s1 - s0) * WAVE, BLOCK_THREADS), BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, s0, s1,
-          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), x->cum32.as<u32>(), cum_stride,
-          (u64)0, 0u, (const u64*)nullptr);
-      }
-      else
-      {
-        LAUNCH("enc_emit", k_enc_emit<false>, div_up((s1 - s0) * WAVE, BLOCK_THREADS), BLOCK_THREADS, x->recs.as<const uint4>(), x->nrecs, x->n, plan.ntiles, s0, s1,
-          plan.lasthead.as<const u64>(), (u64)0, plan.seg_base.as<const u64>(), x->data.as<u8>(), x->block_start.as<u64>(), (u32*)nullptr, (u64)0,
-          (u64)0, 0u, (const u64*)nullptr);
-      }
-      return BWTM_OK;
-    };
-    rc = launch();
+    if(host_out) { while(g1 < enc.ngroups && plan.group_base_host[g1] - plan.group_base_host[g0] < (u64)g_tune.download_chunk) { g1++; } }
+    else { g1 = enc.ngroups; }
+    rc = enc.emit(g0 * FOLD_GROUP, std::min(enc.seg_end, g1 * FOLD_GROUP), x->data.as<u8>(), x->block_start.as<u64>(), x->cum32.as<u32>(), cum_stride);
     if(rc == BWTM_OK && host_out)
     {
       const u64 from = plan.group_base_host[g0], to = plan.group_base_host[g1];
@@ -461,18 +495,11 @@ int encode_emit(bwtm_index* x, EncodePlan& plan, u8* host_out, bool with_cum = f
     g0 = g1;
   }
   if(ev) { (void)hipEventDestroy(ev); }
-  if(rc == BWTM_OK && with_cum)
-  {
-    // the entry behind the last block: the counts at n (every block's own entry was stored by the lane that opened it)
-    auto last = [&]() -> int
-    {
-      LAUNCH("block_cum", k_block_cum32, 1, BLOCK_THREADS, x->recs.as<const uint4>(), x->block_start.as<const u64>(), x->nblocks, (u64)1, x->cum32.as<u32>(), cum_stride);
-      return BWTM_OK;
-    };
-    rc = last();
-  }
   x->has_native = true;
-  return rc;
+  TRY(rc);
+  // the entry behind the last block: the counts at n (every block's own entry was stored by the lane that opened it)
+  if(with_cum) { LAUNCH("block_cum", k_block_cum32, 1, BLOCK_THREADS, x->recs.as<const uint4>(), x->block_start.as<const u64>(), x->nblocks, (u64)1, x->cum32.as<u32>(), cum_stride); }
+  return BWTM_OK;
 }
 
 int encode_blocking(bwtm_index* x)

@@ -10,7 +10,9 @@
        the tables of the slices before it gives a slice its exact byte offset.
 
   Needed for memory (BASELINE config 4: the result does not fit next to the replicated inputs) and for scaling (the
-  interleave / encode / download tail shrinks with the number of GPUs).  Part of bwtm_api.hip.
+  interleave / encode / download tail shrinks with the number of GPUs).  The encoder's kernels are launched by
+  EncodePasses (api/index.hip.h), as for a whole index: bwtm_slice_lasthead, _size_table and _encode run its passes
+  heads, sizes, place + emit and fetch what travels between the slices.  Part of bwtm_api.hip.
 */
 #pragma once
 
@@ -27,12 +29,9 @@ struct bwtm_slice
   u64 rec_halo = 0;                    // first record held (rec_first - 1, or 0)
   DevBuf recs;                         // records [rec_halo, rec_last)
   DevBuf sup; u64 nsup = 0;            // super table of the whole result (small)
-  u64 seg_first = 0, seg_end = 0;      // encoder segments of this slice
   // encoder state
-  DevBuf lasthead, table, group_table, group_base, seg_base;
-  u64 ngroups = 0;
+  EncodePasses enc;                    // the slice's segments, the size tables and the head carry (api/index.hip.h)
   int stage = 0;                       // 0 = interleaved, 1 = lasthead known, 2 = size table known, 3 = encoded
-  u64 head_carry = 0;
   u32 halo_symbol = 0;                 // symbol at position 128 rec_first - 1
   u64 byte_first = 0, byte_end = 0;    // stream offsets of the slice's bytes
   DevBuf data;                         // bytes [byte_first & ~63, byte_end)
@@ -46,12 +45,10 @@ struct bwtm_slice
   // device memory the slice owns now, and the most it owned since a caller last cleared the mark (the size tables live from
   // bwtm_slice_size_table to the end of bwtm_slice_encode)
   u64 bytes_high = 0;
-  u64 device_bytes() const
-  {
-    return recs.bytes + sup.bytes + lasthead.bytes + table.bytes + group_table.bytes + group_base.bytes + seg_base.bytes + data.bytes + block_start.bytes + cum32.bytes;
-  }
+  u64 device_bytes() const { return recs.bytes + sup.bytes + enc.bytes() + data.bytes + block_start.bytes + cum32.bytes; }
 
   const uint4* recs_virtual() const { return recs.as<const uint4>() - 4 * rec_halo; }
+  u8* stream_byte(u64 offset) const { return data.as<u8>() - (byte_first & ~(u64)(RLE_BLOCK - 1)) + offset; }       // device address of a byte of the stream
   u64 pos_first() const { return rec_first << REC_SHIFT; }
   IndexView view() const
   {
@@ -223,9 +220,10 @@ extern "C" int bwtm_interleave_range(const bwtm_index* a, const bwtm_index* b, b
     for(int c = 0; c < 8; c++) { s->C[c] = a->C[c] + b->C[c]; }
     s->nrecs_total = nrecs; s->rec_first = rec_first; s->rec_last = rec_last;
     s->rec_halo = (rec_first > 0 ? rec_first - 1 : 0);
-    if(rec_first < rec_last) { s->seg_first = rec_first / SLICE_ALIGN; s->seg_end = div_up(rec_last, SLICE_ALIGN); }   // an empty slice has no segments
+    if(rec_first < rec_last) { s->enc.seg_first = rec_first / SLICE_ALIGN; s->enc.seg_end = div_up(rec_last, SLICE_ALIGN); }   // an empty slice has no segments
     s->nsup = num_supers(s->n);
     TRY(s->recs.alloc((rec_last - s->rec_halo + 1) * 64));
+    s->enc.recs = s->recs_virtual(); s->enc.nrecs = nrecs; s->enc.n = s->n;
     TRY(s->sup.alloc(s->nsup * SUP_STRIDE * sizeof(u64)));
     if(a->windowed || b->windowed)
     {
@@ -260,19 +258,13 @@ extern "C" int bwtm_slice_lasthead(bwtm_slice* s, uint64_t* lasthead)
 {
   if(!s || !lasthead) { return fail(BWTM_EINVAL, "bwtm_slice_lasthead: null argument"); }
   ENTER(s->ctx);
-  const u64 nseg = s->seg_end - s->seg_first;
+  const u64 nseg = s->enc.nseg();
   *lasthead = 0;
   s->stage = 1;
   if(nseg == 0) { return BWTM_OK; }
-  const u64 ntiles = (s->n >> 6) + 1;
-  TRY(s->lasthead.alloc((nseg + 1) * sizeof(u64)));
-  HIP_TRY(hipMemsetAsync(s->lasthead.as<u64>() + nseg, 0, sizeof(u64), CTX.stream));
-  LAUNCH("enc_lasthead", k_enc_lasthead, div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles,
-    s->seg_first, s->seg_end, s->lasthead.as<u64>() - s->seg_first);
-  // exclusive max-scan over nseg + 1 entries: entry k = (last head of the slice before its segment k) + 1, the extra entry = the slice's own
-  TRY(device_scan<1>(s->lasthead.as<u64>(), s->lasthead.as<u64>(), nseg + 1));
-  if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, s->lasthead.as<const u64>() + nseg, s->host_direct, 1u); }
-  else { TRY(fetch_u64(s->lasthead.as<u64>() + nseg, 0)); }
+  TRY(s->enc.heads(true));                                   // the entry behind the last segment: the slice's own last head
+  if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, s->enc.lasthead.as<const u64>() + nseg, s->host_direct, 1u); }
+  else { TRY(fetch_u64(s->enc.lasthead.as<u64>() + nseg, 0)); }
   // the symbol before the slice (for the samples of blocks opened by a run that began in an earlier slice)
   DevBuf sym; TRY(sym.alloc(8));
   if(s->rec_first > 0)
@@ -297,20 +289,12 @@ extern "C" int bwtm_slice_size_table(bwtm_slice* s, uint64_t heads_before, uint6
   if(!s || !table) { return fail(BWTM_EINVAL, "bwtm_slice_size_table: null argument"); }
   ENTER(s->ctx);
   if(s->stage < 1) { return fail(BWTM_EINVAL, "bwtm_slice_size_table: call bwtm_slice_lasthead first"); }
-  const u64 nseg = s->seg_end - s->seg_first;
-  s->head_carry = heads_before;
   s->stage = 2;
   for(int o = 0; o < 64; o++) { table[o] = 0; }
-  if(nseg == 0) { return BWTM_OK; }
-  const u64 ntiles = (s->n >> 6) + 1;
-  s->ngroups = div_up(nseg, FOLD_GROUP);
-  TRY(s->table.alloc(nseg * 64 * sizeof(u32)));
-  TRY(s->group_table.alloc(s->ngroups * 64 * sizeof(u64)));
+  if(s->enc.nseg() == 0) { return BWTM_OK; }
+  TRY(s->enc.sizes(heads_before));
   DevBuf slice_table; TRY(slice_table.alloc(64 * sizeof(u64)));
-  LAUNCH("enc_size", k_enc_size, div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
-    s->lasthead.as<const u64>() - s->seg_first, heads_before, s->table.as<u32>() - s->seg_first * 64);
-  LAUNCH("fold_group", k_fold_group, s->ngroups, WAVE, s->table.as<const u32>(), nseg, s->group_table.as<u64>());
-  LAUNCH("fold_slice", k_fold_slice, 1, WAVE, s->group_table.as<const u64>(), s->ngroups, slice_table.as<u64>());
+  LAUNCH("fold_slice", k_fold_slice, 1, WAVE, s->enc.group_table.as<const u64>(), s->enc.ngroups, slice_table.as<u64>());
   if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, slice_table.as<const u64>(), s->host_direct + 8, 64u); }
   else { HIP_TRY(hipMemcpyAsync(table, slice_table.p, 64 * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
   HIP_TRY(hipStreamSynchronize(CTX.stream));
@@ -324,47 +308,40 @@ namespace
 int slice_encode(bwtm_slice* s, u64 byte_offset, bool with_cum)
 {
   if(s->stage < 2) { return fail(BWTM_EINVAL, "bwtm_slice_encode: call bwtm_slice_size_table first"); }
-  const u64 nseg = s->seg_end - s->seg_first;
+  EncodePasses& enc = s->enc;
   s->byte_first = byte_offset; s->byte_end = byte_offset;
+  s->block_first = div_up(byte_offset, RLE_BLOCK); s->nblocks = 0;
   s->stage = 3;
-  if(nseg > 0)
+  if(enc.nseg() > 0)
   {
-    const u64 ntiles = (s->n >> 6) + 1;
-    TRY(s->group_base.alloc((s->ngroups + 1) * sizeof(u64)));
-    TRY(s->seg_base.alloc(nseg * sizeof(u64)));
-    LAUNCH("fold_top", k_fold_top, 1, WAVE, s->group_table.as<const u64>(), s->ngroups, byte_offset, s->group_base.as<u64>());
-    LAUNCH("fold_seg", k_fold_seg, s->ngroups, WAVE, s->table.as<const u32>(), nseg, s->group_base.as<const u64>(), s->seg_base.as<u64>());
-    if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, s->group_base.as<const u64>() + s->ngroups, s->host_direct, 1u); }
-    else { TRY(fetch_u64(s->group_base.as<u64>() + s->ngroups, 0)); }
+    TRY(enc.place(byte_offset));
+    if(s->host_direct) { LAUNCH("store_host", k_store_host, 1, WAVE, enc.group_base.as<const u64>() + enc.ngroups, s->host_direct, 1u); }
+    else { TRY(fetch_u64(enc.group_base.as<u64>() + enc.ngroups, 0)); }
     HIP_TRY(hipStreamSynchronize(CTX.stream));
     s->byte_end = (s->host_direct ? s->host_direct[0] : CTX.host_scratch[0]);
-    const u64 base = byte_offset & ~(u64)(RLE_BLOCK - 1);
-    s->block_first = div_up(byte_offset, RLE_BLOCK);
     s->nblocks = div_up(s->byte_end, RLE_BLOCK) - s->block_first;
-    TRY(alloc_native(s->data, s->byte_end - base));
+    TRY(alloc_native(s->data, s->byte_end - (byte_offset & ~(u64)(RLE_BLOCK - 1))));
     TRY(s->block_start.alloc((s->nblocks + 1) * sizeof(u64), true));
+    // block_start and cum32 hold the slice's blocks only: both are indexed by the global block number through shifted pointers
+    u64* starts = s->block_start.as<u64>() - s->block_first;
     if(with_cum && s->nblocks > 0)
     {
-      // block_start and cum32 hold the slice's blocks only: both are indexed by the global block number through shifted pointers
       TRY(s->cum32.alloc(5 * s->nblocks * sizeof(u32)));
-      LAUNCH("enc_emit", (k_enc_emit<true, true>), div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
-        s->lasthead.as<const u64>() - s->seg_first, s->head_carry, s->seg_base.as<const u64>() - s->seg_first, s->data.as<u8>() - base,
-        s->block_start.as<u64>() - s->block_first, s->cum32.as<u32>() - s->block_first, s->nblocks, s->pos_first(), s->halo_symbol, s->sup.as<const u64>());
+      TRY(enc.emit(enc.seg_first, enc.seg_end, s->stream_byte(0), starts, s->cum32.as<u32>() - s->block_first, s->nblocks, s->pos_first(), s->halo_symbol, s->sup.as<const u64>()));
     }
-    else
-    {
-      LAUNCH("enc_emit", k_enc_emit<false>, div_up(nseg * WAVE, BLOCK_THREADS), BLOCK_THREADS, s->recs_virtual(), s->nrecs_total, s->n, ntiles, s->seg_first, s->seg_end,
-        s->lasthead.as<const u64>() - s->seg_first, s->head_carry, s->seg_base.as<const u64>() - s->seg_first, s->data.as<u8>() - base,
-        s->block_start.as<u64>() - s->block_first, (u32*)nullptr, (u64)0, (u64)0, 0u, (const u64*)nullptr);
-    }
+    else { TRY(enc.emit(enc.seg_first, enc.seg_end, s->stream_byte(0), starts, nullptr, 0)); }
   }
-  else
-  {
-    s->block_first = div_up(byte_offset, RLE_BLOCK); s->nblocks = 0;
-    TRY(s->block_start.alloc(sizeof(u64), true));
-  }
+  else { TRY(s->block_start.alloc(sizeof(u64), true)); }
   s->bytes_high = std::max(s->bytes_high, s->device_bytes());
-  s->table.release(); s->group_table.release(); s->group_base.release(); s->seg_base.release(); s->lasthead.release();
+  enc.release();
+  return BWTM_OK;
+}
+
+// The six cumulative counts at the starts of the slice's blocks, one rank query each: 6 rows of nblocks u64.
+int slice_block_cum(bwtm_slice* s, u64* cum)
+{
+  LAUNCH("block_cum", k_block_cum_slice, div_up(s->nblocks, BLOCK_THREADS), BLOCK_THREADS, s->view(), s->block_start.as<const u64>(), (u64)0, s->nblocks, cum, s->nblocks,
+    s->pos_first(), s->halo_symbol);
   return BWTM_OK;
 }
 } // namespace
@@ -401,11 +378,7 @@ extern "C" int bwtm_slice_download_data(bwtm_slice* s, uint8_t* out, uint64_t ca
   if(s->stage < 3) { return fail(BWTM_EINVAL, "bwtm_slice_download_data: slice not encoded"); }
   const u64 bytes = s->byte_end - s->byte_first;
   if(capacity < bytes) { return fail(BWTM_EINVAL, "bwtm_slice_download_data: buffer too small"); }
-  if(bytes > 0)
-  {
-    const u64 base = s->byte_first & ~(u64)(RLE_BLOCK - 1);
-    HIP_TRY(hipMemcpyAsync(out, s->data.as<u8>() + (s->byte_first - base), bytes, hipMemcpyDeviceToHost, CTX.stream));
-  }
+  if(bytes > 0) { HIP_TRY(hipMemcpyAsync(out, s->stream_byte(s->byte_first), bytes, hipMemcpyDeviceToHost, CTX.stream)); }
   HIP_TRY(hipStreamSynchronize(CTX.stream));
   return BWTM_OK;
 }
@@ -423,8 +396,7 @@ extern "C" int bwtm_slice_download_samples(bwtm_slice* s, uint64_t next_block_st
   DevBuf be, dc;
   TRY(be.alloc(nb * sizeof(u64))); TRY(dc.alloc(6 * nb * sizeof(u64)));
   LAUNCH("block_end", k_block_end, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, s->block_start.as<const u64>(), (u64)0, nb, be.as<u64>());
-  LAUNCH("block_cum", k_block_cum_slice, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, s->view(), s->block_start.as<const u64>(), (u64)0, nb, dc.as<u64>(), nb,
-    s->pos_first(), s->halo_symbol);
+  TRY(slice_block_cum(s, dc.as<u64>()));
   HIP_TRY(hipMemcpyAsync(block_end, be.p, nb * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
   HIP_TRY(hipMemcpyAsync(cum, dc.p, 6 * nb * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
   HIP_TRY(hipStreamSynchronize(CTX.stream));

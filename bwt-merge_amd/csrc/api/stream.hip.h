@@ -159,18 +159,16 @@ struct Streamer
     if(S.nbytes > 0)
     {
       TRY(host_reserve(S.host_data, S.host_data_cap, S.nbytes));
-      const u64 base = s->byte_first & ~(u64)(RLE_BLOCK - 1);
       HIP_TRY(hipEventRecord(S.ready, CTX.stream));
       HIP_TRY(hipStreamWaitEvent(CTX.copy_stream, S.ready, 0));
-      HIP_TRY(hipMemcpyAsync(S.host_data, s->data.as<u8>() + (s->byte_first - base), S.nbytes, hipMemcpyDeviceToHost, CTX.copy_stream));
+      HIP_TRY(hipMemcpyAsync(S.host_data, s->stream_byte(s->byte_first), S.nbytes, hipMemcpyDeviceToHost, CTX.copy_stream));
     }
     if(entries > 0 && (S.ns > 0 || nb > 0))
     {
       if(by_query && nb > 0)
       {
         TRY(S.cumabs.alloc(6 * nb * sizeof(u64)));
-        LAUNCH("block_cum", k_block_cum_slice, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, s->view(), s->block_start.as<const u64>(), (u64)0, nb, S.cumabs.as<u64>(), nb,
-          s->pos_first(), s->halo_symbol);
+        TRY(slice_block_cum(s, S.cumabs.as<u64>()));
       }
       S.src.block_start = s->block_start.as<const u64>();
       S.src.cum32 = (by_query ? (const u32*)nullptr : s->cum32.as<const u32>());

@@ -5,11 +5,12 @@
 
     api/context.hip.h   contexts (device, streams, memory pool), errors, launch macros, profiling, scans
     api/index.hip.h     device index: upload steps, the blocking upload of one index, the pipelined upload of a merge's two inputs,
-                        transcode, canonical encoder + pipelined download, queries
+                        transcode, canonical encoder (EncodePasses: its one driver, for the whole index and for a slice) + pipelined
+                        download, queries
     api/upload_stream.hip.h  the chunked upload: records + super table from a ring of chunk buffers, the stream never resident as a whole
     api/search.hip.h    rank array: frontier search / per-chain walk, finalize, downloads
     api/merge.hip.h     interleave, the merged header, whole-path entry points (device-resident, consuming, host-to-host)
-    api/slices.hip.h    output-range-sharded interleave + encode (one slice per GPU)
+    api/slices.hip.h    output-range-sharded interleave + encode (one slice per GPU): the encoder's passes with the two carries between slices
     api/stream.hip.h    host-to-host merge whose second half runs slice by slice on one GPU, the result handed to the caller in pieces
     api/group.hip.h     the parts of a multi-GPU merge: shared control block (barrier, small all-gathers), exported arenas (raw pointer / HIP IPC)
     api/pmerge.hip.h    the merge over PARTITIONED records, one part per GPU: windows from byte shares, cuts, the routed search, the second half
