@@ -1307,6 +1307,16 @@ def profile_reset():
     check(lib().bwtm_profile_reset())
 
 
+def frontier_step_forms():
+    """Step-kernel launches since the last profile_reset by the form of the frontier's coordinates: (absolute, absolute in and
+    class-relative out, class-relative); counted whether or not profiling is enabled."""
+    f = lib().bwtm_frontier_step_forms      # bound on first use, not with SYMBOLS: a library of an earlier round (BWTM_LIB, the A/B tools) still loads
+    f.restype = C.c_int; f.argtypes = [p_u64]
+    n = (u64 * 3)()
+    check(f(n))
+    return tuple(int(v) for v in n)
+
+
 def profile_read():
     """{kernel name: (total_ms, launches)} since the last reset."""
     cap = 64

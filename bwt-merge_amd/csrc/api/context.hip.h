@@ -73,6 +73,7 @@ struct bwtm_context
   // same time.  The limits come from THIS device (CUs x workgroups of the kernel per CU, capped at FRONTIER_SCAN1_TILES); larger tables take the
   // two-launch form.  (A device that is shared with other processes delays such a kernel, it cannot deadlock it: the others' kernels end.)
   u64 scan1_tiles = 0, pull_scan1_tiles = 0;
+  u64 step_forms[3] = {0, 0, 0};           // k_frontier_step launches per form of the coordinates (REL) since the last bwtm_profile_reset
 };
 
 namespace
@@ -96,6 +97,9 @@ struct Tuning
   long long search_view = 0;              // the frontier search reads the two-plane search view: 0 = never (default: it saves 14 % of the HBM reads and no time), 1 = always, 2 = by size
 #endif
   long long frontier_stage_out = 1;       // k_frontier_step stores the next frontier: 1 = in slot order through LDS (whole lines per wave), 0 = every lane its own element (rounds 1 - 6); changes the kernel's HBM traffic
+  long long frontier_rel = 1;             // k_frontier_step keeps class-relative 32-bit coordinates (no arrays of high bytes): 1 = when an index has 2^32 positions or more and every
+                                          // symbol occurs fewer than 2^32 times in each index, 0 = never, 2 = whenever the counts allow it, also below 2^32 positions (tests);
+                                          // changes the kernel's HBM traffic
   long long frontier_parts = 0;           // > 1: every step of the frontier search as this many launches over slices of the frontier (a measurement, same results)
   long long part_capacity = 0;            // tests: elements a part of the partitioned merge can hold in a step (0 = 2 m / parts + slack): forces the out-of-room
                                           // paths; negative: only the element steps are held to |value| (the roots and the expansion of the node levels are not)
@@ -282,10 +286,22 @@ void profile_collect()
 #define LAUNCH(name, kernel, grid, block, ...) LAUNCH_CFG(name, kernel, grid, 1, block, 0, __VA_ARGS__)
 #define LAUNCH_LDS(name, kernel, grid, block, lds, ...) LAUNCH_CFG(name, kernel, grid, 1, block, lds, __VA_ARGS__)
 #define LAUNCH2D(name, kernel, gridx, gridy, block, ...) LAUNCH_CFG(name, kernel, gridx, gridy, block, 0, __VA_ARGS__)
-// k_frontier_step<EMIT, HI, VIEW, PULL, STAGE>: the form of its stores is chosen per launch (g_tune.frontier_stage_out)
+// k_frontier_step<EMIT, HI, VIEW, PULL, STAGE>: the form of its stores is chosen per launch (g_tune.frontier_stage_out); CTX.step_forms
+// counts the launches per form of the coordinates (bwtm_frontier_step_forms)
 #define LAUNCH_STEP(name, EMIT, HI, VIEW, PULL, grid, ...) do { \
+  CTX.step_forms[0]++; \
   if(g_tune.frontier_stage_out) { LAUNCH(name, (k_frontier_step<EMIT, HI, VIEW, PULL, true>), grid, FR_BLOCK, __VA_ARGS__); } \
   else { LAUNCH(name, (k_frontier_step<EMIT, HI, VIEW, PULL, false>), grid, FR_BLOCK, __VA_ARGS__); } } while(0)
+// k_frontier_step<Rel<REL>, EMIT, HI, STAGE>: the class-relative forms of the plain search
+#define LAUNCH_STEP_FORM(name, EMIT, HI, REL, grid, ...) do { \
+  CTX.step_forms[REL]++; \
+  if(g_tune.frontier_stage_out) { LAUNCH(name, (k_frontier_step<Rel<REL>, EMIT, HI, true>), grid, FR_BLOCK, __VA_ARGS__); } \
+  else { LAUNCH(name, (k_frontier_step<Rel<REL>, EMIT, HI, false>), grid, FR_BLOCK, __VA_ARGS__); } } while(0)
+// The plain search: rel = 0 absolute coordinates, 1 = absolute in and class-relative out (the first step), 2 = class-relative (no high bytes: HI is not read)
+#define LAUNCH_STEP_REL(name, EMIT, HI, rel, grid, ...) do { \
+  if((rel) == 2) { LAUNCH_STEP_FORM(name, EMIT, false, 2, grid, __VA_ARGS__); } \
+  else if((rel) == 1) { LAUNCH_STEP_FORM(name, EMIT, HI, 1, grid, __VA_ARGS__); } \
+  else { LAUNCH_STEP(name, EMIT, HI, false, false, grid, __VA_ARGS__); } } while(0)
 
 //------------------------------------------------------------------------------
 // Pool.
@@ -700,6 +716,7 @@ int tune_set(const char* key, long long value)
   else if(k == "search_view") { g_tune.search_view = (value >= 0 && value <= 2 ? value : 0); }
 #endif
   else if(k == "frontier_stage_out") { g_tune.frontier_stage_out = (value != 0); }
+  else if(k == "frontier_rel") { g_tune.frontier_rel = (value >= 0 && value <= 2 ? value : 1); }
   else if(k == "frontier_parts") { g_tune.frontier_parts = (value > 0 ? value : 0); }
   else if(k == "stream_samples_query") { g_tune.stream_samples_query = (value != 0); }
   else if(k == "stream_upload") { g_tune.stream_upload = (value != 0); }
@@ -844,6 +861,15 @@ extern "C" int bwtm_profile_reset(void)
   ENTER(nullptr);
   profile_collect();
   CTX.totals.clear(); CTX.order.clear();
+  for(int k = 0; k < 3; k++) { CTX.step_forms[k] = 0; }
+  return BWTM_OK;
+}
+
+extern "C" int bwtm_frontier_step_forms(uint64_t launches[3])
+{
+  if(!launches) { return fail(BWTM_EINVAL, "bwtm_frontier_step_forms: null argument"); }
+  ENTER(nullptr);
+  for(int k = 0; k < 3; k++) { launches[k] = CTX.step_forms[k]; }
   return BWTM_OK;
 }
 

@@ -359,10 +359,19 @@ int search_frontier(const bwtm_index* a, const bwtm_index* b, u64 seq_first, u64
 
   // r may equal n_a and LF results stay below n: 32 bits hold every coordinate when both indexes are below 2^32 positions
   const bool wide = (a->n >= (1ull << 32) || b->n >= (1ull << 32));
+  // Class-relative coordinates (frontier_rel; k_frontier_step<.., REL>): an element that came out of class c lies in [C_B[c], C_B[c+1]) x
+  // [C_A[c], C_A[c+1]] (r may equal C_A[c+1], hence the strict bound), so 32 bits hold its offsets in the class when every symbol occurs fewer
+  // than 2^32 times in each index.  The first step reads the absolute form (the roots / the expanded node level sit in row 0 of the table
+  // whatever their symbols are) and writes the relative one; hi[0] serves that step only and hi[1] does not exist.
+  bool rel = (g_tune.frontier_rel == 2 || (g_tune.frontier_rel == 1 && wide));
+  for(int c = 1; c <= 5 && rel; c++) { rel = (a->C[c + 1] - a->C[c] < (1ull << 32) && b->C[c + 1] - b->C[c] < (1ull << 32)); }
+#ifdef BWTM_EXPERIMENTAL
+  if(g_tune.search_view != 0) { rel = false; }                    // the search view keeps the absolute form
+#endif
   DevBuf lo[2], hi[2], seg_len[2], seg_phys[2], seg_prefix, emit16, emit_base, bound;
   for(int k = 0; k < 2; k++)
   {
-    TRY(lo[k].alloc(fcap * 8)); if(wide) { TRY(hi[k].alloc(fcap * 2)); }
+    TRY(lo[k].alloc(fcap * 8)); if(wide && (k == 0 || !rel)) { TRY(hi[k].alloc(fcap * 2)); }
     TRY(seg_len[k].alloc((nseg + 1) * sizeof(u64), true)); TRY(seg_phys[k].alloc((nseg + 1) * sizeof(u64), true));
   }
   TRY(seg_prefix.alloc((nseg + 1) * sizeof(u64)));
@@ -482,9 +491,10 @@ int search_frontier(const bwtm_index* a, const bwtm_index* b, u64 seq_first, u64
     f.nb_max = nb_max;
     f.emit16 = emit16.as<unsigned short>(); f.emit_base = emit_base.as<const u64>(); f.emit_cap = emit_cap; f.bits32 = ra->bits_as<u32>();
     f.bound_row = bound.as<u32>() + in_epoch * (ntiles + 1); f.step = in_epoch; f.block_base = 0; f.src_lo = nullptr; f.src_hi = nullptr; f.nseg_in = 0;
+    const int rel_form = (rel ? (t == 0 ? 1 : 2) : 0);              // the form of this step's coordinates (REL)
 #ifdef BWTM_DIAGNOSTICS
-    if(g_tune.walk_emit == 1 && wide) { LAUNCH_STEP("frontier_step_noemit", 1, true, false, false, grid, a->view(), b->view(), f); }
-    else if(g_tune.walk_emit == 1) { LAUNCH_STEP("frontier_step_noemit", 1, false, false, false, grid, a->view(), b->view(), f); }
+    if(g_tune.walk_emit == 1 && wide) { LAUNCH_STEP_REL("frontier_step_noemit", 1, true, rel_form, grid, a->view(), b->view(), f); }
+    else if(g_tune.walk_emit == 1) { LAUNCH_STEP_REL("frontier_step_noemit", 1, false, rel_form, grid, a->view(), b->view(), f); }
     else
 #endif
     if(g_tune.frontier_parts > 1)
@@ -497,16 +507,17 @@ int search_frontier(const bwtm_index* a, const bwtm_index* b, u64 seq_first, u64
         f.block_base = (u32)(part * per);
         const u64 nb_part = std::min<u64>(per, nb_max - part * per);
         const char* label = (part == 0 ? "frontier_step_slice0" : "frontier_step_slices");
-        if(wide) { LAUNCH_STEP(label, 0, true, false, false, nb_part, a->view(), b->view(), f); }
-        else { LAUNCH_STEP(label, 0, false, false, false, nb_part, a->view(), b->view(), f); }
+        if(wide) { LAUNCH_STEP_REL(label, 0, true, rel_form, nb_part, a->view(), b->view(), f); }
+        else { LAUNCH_STEP_REL(label, 0, false, rel_form, nb_part, a->view(), b->view(), f); }
       }
     }
 #ifdef BWTM_EXPERIMENTAL
     else if(use_view && wide) { LAUNCH_STEP("frontier_step", 0, true, true, false, grid, a->view(), b->view(), f); }
     else if(use_view) { LAUNCH_STEP("frontier_step", 0, false, true, false, grid, a->view(), b->view(), f); }
 #endif
-    else if(wide) { LAUNCH_STEP("frontier_step", 0, true, false, false, grid, a->view(), b->view(), f); }
-    else { LAUNCH_STEP("frontier_step", 0, false, false, false, grid, a->view(), b->view(), f); }
+    else if(wide) { LAUNCH_STEP_REL("frontier_step", 0, true, rel_form, grid, a->view(), b->view(), f); }
+    else { LAUNCH_STEP_REL("frontier_step", 0, false, rel_form, grid, a->view(), b->view(), f); }
+    if(rel && t == 0) { hi[0].release(); }                          // (stream order: the pool hands it out to work queued behind this step only)
     // the size of step t reaches the host behind step t's kernels: recorded AFTER the step kernel, so that reduce, scan and step
     // follow each other without another command between them
     if(size_in_ring) { HIP_TRY(hipEventRecord(events.ev[t % LOOK], CTX.stream)); }

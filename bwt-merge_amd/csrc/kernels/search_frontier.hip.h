@@ -134,12 +134,22 @@ __device__ inline u64 ordinary_lf(const IndexView& X, u64 pos, u32& c, bool want
 // 512 contiguous, 512-byte-aligned bytes of lo_next with one instruction; without it every lane stores its own element at its slot position
 // (one run per class and wave, at 8-byte alignment).  The same values reach the same addresses either way; the staged form sends a tenth fewer
 // write requests to memory and is the faster one at every shape measured (profiles/r07_stage_out_ab.txt).
-template<int EMIT, bool HI, bool VIEW = false, bool PULL = false, bool STAGE = false>
-__global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(IndexView A, IndexView B, FrontierView f)
+// REL (BWTM_TUNE frontier_rel, chosen by search_frontier): the form of the coordinates in the frontier buffers.  An element that came out of
+// class c has i in [C_B[c], C_B[c+1]) and r in [C_A[c], C_A[c+1]], and its reader knows c: it is the row of the segment table the element is
+// found through (segment / nb_max = c - 1).  When every symbol occurs fewer than 2^32 times in each index, i - C_B[c] and r - C_A[c] fit the
+// 8-byte entry and the 2-byte array of high bytes is not needed, whatever the size of the indexes.
+//   0 = absolute coordinates in and out (with the high bytes when HI);
+//   1 = read in absolute form (with the high bytes when HI), written class-relative: the first step, whose input (the roots or the
+//       expanded node level) sits in row 0 of the table whatever its symbols are;
+//   2 = read and written class-relative: neither f.hi nor f.hi_next is touched (HI is false).
+template<int EMIT, bool HI, bool VIEW, bool PULL, bool STAGE, int REL>
+__device__ __forceinline__ void frontier_step_body(const IndexView A, const IndexView B, const FrontierView f)
 {
+  static_assert(REL >= 0 && REL <= 2 && (REL == 0 || (!VIEW && !PULL)) && (REL != 2 || !HI), "class-relative coordinates: the plain search only");
+  constexpr bool HI_OUT = (HI && REL == 0);                       // the next frontier has high bytes
   __shared__ u32 wave_cnt[FR_BLOCK / WAVE][6];
   __shared__ uint2 s_out[STAGE ? FR_BLOCK : 1];
-  __shared__ unsigned short s_out_hi[STAGE && HI ? FR_BLOCK : 1];
+  __shared__ unsigned short s_out_hi[STAGE && HI_OUT ? FR_BLOCK : 1];
   __shared__ u64 s_prefix[FR_SEGS + 1], s_phys[FR_SEGS + 1];
   __shared__ const uint2* s_src_lo[PULL ? 16 : 1];
   __shared__ const unsigned short* s_src_hi[PULL ? 16 : 1];
@@ -177,14 +187,14 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
   u64 i = 0, r = 0;
   if(active)
   {
-    u64 phys;
+    u64 phys, seg;
     // the staged entry that holds g: the largest k with s_prefix[k] <= g (empty segments repeat their neighbour's prefix).  Five
     // steps of a binary search: the linear walk was unrolled by the compiler into 31 compare-select steps on 64-bit values,
     // ~190 of the kernel's ~470 VALU instructions per wave.
     u32 k = 0;
 #pragma unroll
     for(u32 step = 16; step != 0; step >>= 1) { if(s_prefix[k + step] <= g) { k += step; } }     // k + step <= 31 = FR_SEGS: inside the FR_SEGS + 1 staged entries
-    if(k < (u32)FR_SEGS) { phys = s_phys[k] + (g - s_prefix[k]); }      // (PULL: the part in the top byte survives the addition)
+    if(k < (u32)FR_SEGS) { seg = first_seg + k; phys = s_phys[k] + (g - s_prefix[k]); }      // (PULL: the part in the top byte survives the addition)
     else
     {
       // Rare: the element lies beyond the staged entries.  Binary search of seg_prefix (non-decreasing) for the segment
@@ -198,6 +208,7 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
         if(f.seg_prefix[mid] <= g) { lo_s = mid; } else { hi_s = mid; }
       }
       const u64 sgm = lo_s;
+      seg = sgm;
       phys = f.seg_phys[sgm] + (g - f.seg_prefix[sgm]);
     }
     const uint2* lo_src = f.lo; const unsigned short* hi_src = f.hi;
@@ -213,6 +224,13 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
     __builtin_amdgcn_sched_barrier(0);      // both loads are issued before either is used (the scheduler otherwise waits for the high bytes before it issues the other load: one more round trip per wave)
     i = (u64)l.x | ((u64)(h & 0xFF) << 32);
     r = (u64)l.y | ((u64)(h >> 8) << 32);
+    if(REL == 2)
+    {
+      // class-relative: the element's class is the row of its segment (compares against multiples of nb_max, selects on the arguments)
+      const u64 nb1 = f.nb_max, nb2 = 2 * f.nb_max, nb3 = 3 * f.nb_max, nb4 = 4 * f.nb_max;
+      i += (seg < nb1 ? B.C[1] : (seg < nb2 ? B.C[2] : (seg < nb3 ? B.C[3] : (seg < nb4 ? B.C[4] : B.C[5]))));
+      r += (seg < nb1 ? A.C[1] : (seg < nb2 ? A.C[2] : (seg < nb3 ? A.C[3] : (seg < nb4 ? A.C[4] : A.C[5]))));
+    }
   }
   const u64 any_active = __ballot(active);
   u32 tile_first = 0xFFFFFFFFu, tile_last = 0xFFFFFFFFu;           // tiles of the wave's first / last element (EMIT == 0)
@@ -331,10 +349,14 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
         {
           ni += supb;
           nr = supa + rec_header(wa, c) + rec_count(wa, c, ja);
-          // C[c]: kernel arguments cannot be indexed dynamically without scratch, hence the selects
-          u64 cb = (c == 1 ? B.C[1] : (c == 2 ? B.C[2] : (c == 3 ? B.C[3] : (c == 4 ? B.C[4] : B.C[5]))));
-          u64 ca = (c == 1 ? A.C[1] : (c == 2 ? A.C[2] : (c == 3 ? A.C[3] : (c == 4 ? A.C[4] : A.C[5]))));
-          ni += cb; nr += ca;                                     // LF_B(i), LF_A(r, c): utils.h:335-348
+          if(REL == 0)
+          {
+            // C[c]: kernel arguments cannot be indexed dynamically without scratch, hence the selects
+            u64 cb = (c == 1 ? B.C[1] : (c == 2 ? B.C[2] : (c == 3 ? B.C[3] : (c == 4 ? B.C[4] : B.C[5]))));
+            u64 ca = (c == 1 ? A.C[1] : (c == 2 ? A.C[2] : (c == 3 ? A.C[3] : (c == 4 ? A.C[4] : A.C[5]))));
+            ni += cb; nr += ca;                                   // LF_B(i), LF_A(r, c): utils.h:335-348
+          }
+          // (REL >= 1: the ranks inside class c are what is stored, below 2^32 by the driver's guard; the next step adds C[c])
         }
       }
     }
@@ -377,7 +399,7 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
     {
       const u32 at = class_base + before_waves + my_rank;               // < the block's number of survivors <= FR_BLOCK
       s_out[at] = make_uint2((u32)ni, (u32)nr);
-      if(HI) { s_out_hi[at] = (unsigned short)(((ni >> 32) & 0xFF) | (((nr >> 32) & 0xFF) << 8)); }
+      if(HI_OUT) { s_out_hi[at] = (unsigned short)(((ni >> 32) & 0xFF) | (((nr >> 32) & 0xFF) << 8)); }
     }
     // the same LDS-only barrier as above: the emits are still in flight
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -385,12 +407,12 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
     asm volatile("" ::: "memory");
     const u32 survivors = tot_k[1] + tot_k[2] + tot_k[3] + tot_k[4] + tot_k[5];
     const uint2 v = s_out[threadIdx.x];                                 // unconditional: only the stores are predicated
-    const unsigned short vh = (HI ? s_out_hi[threadIdx.x] : (unsigned short)0);
+    const unsigned short vh = (HI_OUT ? s_out_hi[threadIdx.x] : (unsigned short)0);
     if(threadIdx.x < survivors)
     {
       // a full wave writes four whole 128-byte lines of lo_next (the slot is 2 KiB aligned), and no line is written by two waves
       nt_store(&f.lo_next[g0 + threadIdx.x], v);
-      if(HI) { nt_store(&f.hi_next[g0 + threadIdx.x], vh); }
+      if(HI_OUT) { nt_store(&f.hi_next[g0 + threadIdx.x], vh); }
     }
   }
   else if(active && c != 0)
@@ -399,7 +421,7 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
     // streaming stores (nt_store): the next frontier and the emits are not read again by this launch; past the L2 they leave it to the records
     // (-2 to -3 ms of 92 per merge at config 2, profiles/r05_nt_stores_ab.txt; non-temporal LOADS of the coordinates on top: no change)
     nt_store(&f.lo_next[dst], make_uint2((u32)ni, (u32)nr));
-    if(HI) { nt_store(&f.hi_next[dst], (unsigned short)(((ni >> 32) & 0xFF) | (((nr >> 32) & 0xFF) << 8))); }
+    if(HI_OUT) { nt_store(&f.hi_next[dst], (unsigned short)(((ni >> 32) & 0xFF) | (((nr >> 32) & 0xFF) << 8))); }
   }
   if(wave == 0)
   {
@@ -415,6 +437,22 @@ __global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(Inde
     if(bid == 0 && threadIdx.x == 5) { f.seg_len_next[nseg_out] = 0; }
   }
   if(mark_first) { atomicMin(&f.bound_row[tile_first], (u32)g); }
+}
+
+// The absolute form (REL = 0) under the template parameters it has had since round 7 ...
+template<int EMIT, bool HI, bool VIEW = false, bool PULL = false, bool STAGE = false>
+__global__ void __launch_bounds__(FR_BLOCK, (VIEW ? 6 : 8)) k_frontier_step(IndexView A, IndexView B, FrontierView f)
+{
+  frontier_step_body<EMIT, HI, VIEW, PULL, STAGE, 0>(A, B, f);
+}
+
+// ... and the class-relative forms of the plain search as an overload whose first argument names the form: k_frontier_step<Rel<1>, ..> and
+// k_frontier_step<Rel<2>, ..>.  (One kernel name for the profiles and counters; the symbols of the absolute instantiations stay what they were.)
+template<int REL> struct Rel { static constexpr int value = REL; };
+template<class FORM, int EMIT, bool HI, bool STAGE>
+__global__ void __launch_bounds__(FR_BLOCK, 8) k_frontier_step(IndexView A, IndexView B, FrontierView f)
+{
+  frontier_step_body<EMIT, HI, false, false, STAGE, FORM::value>(A, B, f);
 }
 
 // Per-step bookkeeping.  first_seg[b] = the segment that holds logical element b * FR_BLOCK: a segment

@@ -588,6 +588,10 @@ int bwtm_profile_enable(int on);
    dominant kernel's durations brackets only that kernel. */
 int bwtm_profile_only(const char* name);
 int bwtm_profile_reset(void);
+/* Launches of the frontier search's step kernel since the last bwtm_profile_reset (counted whether or not profiling is enabled), by the
+   form of the frontier's coordinates: [0] absolute in and out, [1] absolute in and class-relative out (the first step of a search that
+   takes the class-relative form), [2] class-relative in and out (bwtm_tune "frontier_rel"). */
+int bwtm_frontier_step_forms(uint64_t launches[3]);
 /* Per-kernel totals since the last reset: returns the number of distinct kernels; fills up to
    `capacity` entries.  names[k] points to a static string. */
 int bwtm_profile_read(const char** names, double* total_ms, uint64_t* launches, int capacity);

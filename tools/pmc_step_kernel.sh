@@ -5,7 +5,9 @@
 # Usage (on the GPU box): bash tools/pmc_step_kernel.sh <out-subdir-of-gpurun_out> <reads per set> [extra bench args]
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$1; reads=$2; shift; shift
 mkdir -p $out; : > $out/pmc.txt
+# PMC_STEP_WRREQ=1: one more pass for the write requests (TCC_EA0_WRREQ, TCC_EA0_WRREQ_64B)
 sets=("FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_128B_sum")
+if [ "$PMC_STEP_WRREQ" = "1" ]; then sets+=("TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"); fi
 cd /tmp
 i=0
 for set in "${sets[@]}"; do
