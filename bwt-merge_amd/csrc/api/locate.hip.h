@@ -18,10 +18,7 @@ struct bwtm_locator
 
 namespace
 {
-// four lanes per walk and fewer than 2^32 threads per grid (the note at LAUNCH_CFG): a batch is one launch
-constexpr u64 LOCATE_BATCH_LIMIT = 1ull << 28;
-
-u64 locate_batch_size() { return std::min<u64>((u64)g_tune.locate_batch, LOCATE_BATCH_LIMIT); }
+u64 locate_batch_size() { return std::min<u64>((u64)g_tune.locate_batch, WALK_BATCH_LIMIT); }
 
 // The table of `loc`: filled with LOCATE_UNSET, one k_locate_build per batch of sequences, then the count of entries nobody claimed.
 int locator_build(bwtm_locator* loc)
@@ -30,27 +27,28 @@ int locator_build(bwtm_locator* loc)
   const u64 m = x->m;
   TRY(loc->table.alloc(m * sizeof(u64)));
   if(m == 0) { return BWTM_OK; }
-  DevBuf d_status;
-  TRY(d_status.alloc(2 * sizeof(u64)));                                                         // the walks' status, the check's count
+  StatusCell status;
+  DevBuf d_unclaimed;                                                                           // the check's count
+  TRY(status.alloc()); TRY(d_unclaimed.alloc(sizeof(u64)));
   HIP_TRY(hipMemsetAsync(loc->table.p, 0xFF, m * sizeof(u64), CTX.stream));                     // LOCATE_UNSET
   const u64 batch = std::min(locate_batch_size(), m);
   for(u64 done = 0; done < m; done += batch)
   {
     const u64 nb = std::min(batch, m - done);
-    HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                         // SEQ_STATUS_NONE
+    TRY(status.arm());
     LAUNCH("locate_build", k_locate_build, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), done, nb, (u32)loc->max_len, loc->table.as<u64>(),
-      d_status.as<unsigned long long>());
-    TRY(fetch_u64(d_status.as<u64>(), 0));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    if(CTX.host_scratch[0] != SEQ_STATUS_NONE)
+      status.word());
+    u64 bad = 0;
+    TRY(status.read(&bad));
+    if(bad != SEQ_STATUS_NONE)
     {
       return fail(BWTM_EINVAL, "bwtm_locator_create: sequence %llu is longer than max_len = %llu (or the index is damaged)",
-        (unsigned long long)(done + CTX.host_scratch[0]), (unsigned long long)loc->max_len);
+        (unsigned long long)(done + bad), (unsigned long long)loc->max_len);
     }
   }
-  HIP_TRY(hipMemsetAsync(d_status.as<u64>() + 1, 0, sizeof(u64), CTX.stream));
-  LAUNCH("locate_check", k_locate_check, std::min<u64>(div_up(m, BLOCK_THREADS), 1024), BLOCK_THREADS, loc->table.as<const u64>(), m, d_status.as<unsigned long long>() + 1);
-  TRY(fetch_u64(d_status.as<u64>() + 1, 0));
+  HIP_TRY(hipMemsetAsync(d_unclaimed.p, 0, sizeof(u64), CTX.stream));
+  LAUNCH("locate_check", k_locate_check, std::min<u64>(div_up(m, BLOCK_THREADS), 1024), BLOCK_THREADS, loc->table.as<const u64>(), m, d_unclaimed.as<unsigned long long>());
+  TRY(fetch_u64(d_unclaimed.as<u64>(), 0));
   HIP_TRY(hipStreamSynchronize(CTX.stream));
   if(CTX.host_scratch[0] != 0)
   {
@@ -63,24 +61,23 @@ int locator_build(bwtm_locator* loc)
 // The device buffers of one batch of hits, and its launch.
 struct LocateBatch
 {
-  DevBuf d_pos, d_start, d_first, d_ids, d_offs, d_status;
+  DevBuf d_pos, d_start, d_first, d_ids, d_offs;
+  StatusCell status;
   int alloc(u64 batch, bool positions)
   {
     if(positions) { TRY(d_pos.alloc(batch * sizeof(u64))); }
     else { TRY(d_start.alloc(batch * sizeof(u64))); TRY(d_first.alloc(batch * sizeof(u64))); }
-    TRY(d_ids.alloc(batch * sizeof(u64))); TRY(d_offs.alloc(batch * sizeof(u64))); TRY(d_status.alloc(sizeof(u64)));
+    TRY(d_ids.alloc(batch * sizeof(u64))); TRY(d_offs.alloc(batch * sizeof(u64))); TRY(status.alloc());
     return BWTM_OK;
   }
   // nb hits (positions in d_pos, or `nranges` ranges in d_start / d_first) -> out_ids / out_offsets; *bad = the first slot that failed, or SEQ_STATUS_NONE
   int run(const bwtm_locator* loc, bool positions, u64 nranges, u64 nb, u64* out_ids, u64* out_offsets, u64* bad)
   {
-    HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                         // SEQ_STATUS_NONE
+    TRY(status.arm());
     LAUNCH("locate", k_locate, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, loc->index->view(), loc->table.as<const u64>(),
       (positions ? d_pos.as<const u64>() : (const u64*)nullptr), d_start.as<const u64>(), d_first.as<const u64>(), nranges, nb, (u32)loc->max_len,
-      d_ids.as<u64>(), d_offs.as<u64>(), d_status.as<unsigned long long>());
-    TRY(fetch_u64(d_status.as<u64>(), 0));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    *bad = CTX.host_scratch[0];
+      d_ids.as<u64>(), d_offs.as<u64>(), status.word());
+    TRY(status.read(bad));
     if(*bad != SEQ_STATUS_NONE) { return BWTM_OK; }                                             // nothing of a failed batch reaches the caller
     HIP_TRY(hipMemcpyAsync(out_ids, d_ids.p, nb * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
     HIP_TRY(hipMemcpyAsync(out_offsets, d_offs.p, nb * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
@@ -96,8 +93,7 @@ extern "C" int bwtm_locator_create(const bwtm_index* x, uint64_t max_len, bwtm_l
   if(!x || !out) { return fail(BWTM_EINVAL, "bwtm_locator_create: null argument"); }
   WHOLE_INDEX(x, "bwtm_locator_create");
   ENTER(x->ctx);
-  if(max_len == 0) { max_len = SEQ_MAX_LEN_DEFAULT; }
-  if(max_len > SEQ_MAX_LEN_LIMIT) { return fail(BWTM_EINVAL, "bwtm_locator_create: max_len %llu is above 2^24", (unsigned long long)max_len); }
+  TRY(check_max_len("bwtm_locator_create", &max_len));
   bwtm_locator* loc = new bwtm_locator();
   loc->index = x; loc->max_len = max_len;
   const int rc = locator_build(loc);

@@ -6,10 +6,7 @@
 
 namespace
 {
-// four lanes per query and fewer than 2^32 threads per grid (the note at LAUNCH_CFG): a batch is one launch
-constexpr u64 OVERLAP_BATCH_LIMIT = 1ull << 28;
-
-u64 overlap_batch_size() { return std::min<u64>((u64)g_tune.overlap_batch, OVERLAP_BATCH_LIMIT); }
+u64 overlap_batch_size() { return std::min<u64>((u64)g_tune.overlap_batch, WALK_BATCH_LIMIT); }
 
 // One batch of queries whose text and offsets are on the device: the count pass, two scans on the device that turn its counts into the
 // first record and the first hit slot of every query, the emit pass and the expansion in hit batches of locate_batch.  Of the counts only
@@ -22,13 +19,14 @@ struct OverlapBatch
   DevBuf d_rbase;       // batch + 1: intervals per query, scanned in place into the first record of every query
   DevBuf d_nhits;       // batch: hits per query before max_hits
   DevBuf d_hbase;       // batch + 1: hits kept per query, scanned in place into the first hit slot of every query
-  DevBuf d_recs, d_ids, d_len, d_status;
+  DevBuf d_recs, d_ids, d_len;
+  StatusCell status;
   u64 nrecs = 0, kept_total = 0;
 
   int alloc(u64 batch)
   {
     TRY(d_rbase.alloc((batch + 1) * sizeof(u64))); TRY(d_nhits.alloc(batch * sizeof(u64))); TRY(d_hbase.alloc((batch + 1) * sizeof(u64)));
-    TRY(d_status.alloc(sizeof(u64)));
+    TRY(status.alloc());
     return BWTM_OK;
   }
   OverlapRecs recs() const
@@ -83,12 +81,12 @@ struct OverlapBatch
     for(u64 done = 0; done < kept_total; done += batch)
     {
       const u64 nh = std::min(batch, kept_total - done);
-      HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                       // SEQ_STATUS_NONE
+      TRY(status.arm());
       LAUNCH("overlap_expand", k_overlap_expand, div_up(nh, BLOCK_THREADS), BLOCK_THREADS, loc->table.as<const u64>(), loc->index->m, recs(), nrecs, done, nh,
-        d_ids.as<u64>(), d_len.as<u64>(), d_status.as<unsigned long long>());
-      TRY(fetch_u64(d_status.as<u64>(), 0));
-      HIP_TRY(hipStreamSynchronize(CTX.stream));
-      if(CTX.host_scratch[0] != SEQ_STATUS_NONE) { *bad = done + CTX.host_scratch[0]; return BWTM_OK; }   // nothing of a failed batch reaches the caller
+        d_ids.as<u64>(), d_len.as<u64>(), status.word());
+      u64 slot = 0;
+      TRY(status.read(&slot));
+      if(slot != SEQ_STATUS_NONE) { *bad = done + slot; return BWTM_OK; }                         // nothing of a failed batch reaches the caller
       HIP_TRY(hipMemcpyAsync(out_ids + done, d_ids.p, nh * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
       HIP_TRY(hipMemcpyAsync(out_lengths + done, d_len.p, nh * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
       HIP_TRY(hipStreamSynchronize(CTX.stream));                                                // the batch's buffers are reused
@@ -192,20 +190,7 @@ extern "C" int bwtm_overlap_sequences(const bwtm_locator* loc, const uint64_t* i
   if(min_overlap == 0) { return fail(BWTM_EINVAL, "bwtm_overlap_sequences: min_overlap must be at least 1"); }
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  if(!ids)
-  {
-    if(first_id >= x->m || count > x->m - first_id)
-    {
-      return fail(BWTM_EINVAL, "bwtm_overlap_sequences: sequence %llu out of range (%llu sequences)", (unsigned long long)std::max<u64>(first_id, x->m), (unsigned long long)x->m);
-    }
-  }
-  else
-  {
-    for(u64 k = 0; k < count; k++)
-    {
-      if(ids[k] >= x->m) { return fail(BWTM_EINVAL, "bwtm_overlap_sequences: sequence %llu out of range (%llu sequences)", (unsigned long long)ids[k], (unsigned long long)x->m); }
-    }
-  }
+  TRY(check_sequence_ids("bwtm_overlap_sequences", x, ids, first_id, count));
   SeqBatch s;
   TRY(s.alloc(std::min(overlap_batch_size(), count), ids != nullptr, true, false));           // lengths and offsets stay on the device
   auto prepare = [&](u64 done, u64 nb, const u8** text_out, const u64** off_out) -> int

@@ -6,15 +6,67 @@
 
 namespace
 {
+// What the per-chain queries share on the host (this file, api/locate.hip.h, api/overlap.hip.h; their kernels: kernels/quad.hip.h).
+
 constexpr u64 SEQ_MAX_LEN_DEFAULT = 1ull << 16, SEQ_MAX_LEN_LIMIT = 1ull << 24;
-// four lanes per sequence and fewer than 2^32 threads per grid (the note at LAUNCH_CFG): a batch is one launch
-constexpr u64 SEQ_BATCH_LIMIT = 1ull << 28;
+// four lanes per sequence, walk or query and fewer than 2^32 threads per grid (the note at LAUNCH_CFG): a batch is one launch
+constexpr u64 WALK_BATCH_LIMIT = 1ull << 28;
+
+// The status word of a launch: its kernel lowers it (atomicMin) to the first slot of the batch that failed.  arm() fills it with 0xFF
+// bytes, which is SEQ_STATUS_NONE; read() queues its copy into slot 0 of the host scratch behind whatever the caller has queued since the
+// launch, awaits the stream and hands the word out.
+struct StatusCell
+{
+  static_assert(SEQ_STATUS_NONE == 0xFFFFFFFFFFFFFFFFull, "arm() fills the word with 0xFF bytes");
+  DevBuf d;
+  int alloc() { return d.alloc(sizeof(u64)); }
+  unsigned long long* word() const { return d.as<unsigned long long>(); }
+  int arm()
+  {
+    HIP_TRY(hipMemsetAsync(d.p, 0xFF, sizeof(u64), CTX.stream));
+    return BWTM_OK;
+  }
+  int read(u64* first_bad)
+  {
+    TRY(fetch_u64(d.as<u64>(), 0));
+    HIP_TRY(hipStreamSynchronize(CTX.stream));
+    *first_bad = CTX.host_scratch[0];
+    return BWTM_OK;
+  }
+};
+
+// max_len of a call: 0 stands for the default, and no walk is allowed more than 2^24 steps.
+int check_max_len(const char* who, u64* max_len)
+{
+  if(*max_len == 0) { *max_len = SEQ_MAX_LEN_DEFAULT; }
+  if(*max_len > SEQ_MAX_LEN_LIMIT) { return fail(BWTM_EINVAL, "%s: max_len %llu is above 2^24", who, (unsigned long long)*max_len); }
+  return BWTM_OK;
+}
+
+// The sequences of a call, count >= 1 of them: ids[0 .. count), or first_id .. first_id + count - 1 (ids == nullptr), are all below m.
+int check_sequence_ids(const char* who, const bwtm_index* x, const u64* ids, u64 first_id, u64 count)
+{
+  if(!ids)
+  {
+    if(first_id >= x->m || count > x->m - first_id)
+    {
+      return fail(BWTM_EINVAL, "%s: sequence %llu out of range (%llu sequences)", who, (unsigned long long)std::max<u64>(first_id, x->m), (unsigned long long)x->m);
+    }
+    return BWTM_OK;
+  }
+  for(u64 k = 0; k < count; k++)
+  {
+    if(ids[k] >= x->m) { return fail(BWTM_EINVAL, "%s: sequence %llu out of range (%llu sequences)", who, (unsigned long long)ids[k], (unsigned long long)x->m); }
+  }
+  return BWTM_OK;
+}
 
 // The per-batch stage of reading sequences by id, shared by bwtm_sequences_extract (which brings the text to the host) and
 // bwtm_overlap_sequences (which searches it where it is): the device buffers of one batch and its two launches.
 struct SeqBatch
 {
-  DevBuf d_ids, d_len, d_off, d_status, d_text;
+  DevBuf d_ids, d_len, d_off, d_text;
+  StatusCell status;
   std::vector<u32> h_len;               // the batch's lengths, after lengths()
   std::vector<u64> h_off;               // batch-local offsets (nb + 1 entries), filled by the caller between lengths() and emit()
   bool on_host = true;                  // false: the lengths stay in d_len, and the caller leaves the nb + 1 offsets in d_off before emit()
@@ -22,7 +74,7 @@ struct SeqBatch
   {
     on_host = host_side;
     if(with_ids) { TRY(d_ids.alloc(batch * sizeof(u64))); }
-    TRY(d_len.alloc(batch * sizeof(u32))); TRY(d_status.alloc(sizeof(u64)));
+    TRY(d_len.alloc(batch * sizeof(u32))); TRY(status.alloc());
     if(with_text) { TRY(d_off.alloc((batch + 1) * sizeof(u64))); }
     h_len.assign(on_host ? batch : 0, 0);
     h_off.assign(on_host && with_text ? batch + 1 : 0, 0);
@@ -33,14 +85,11 @@ struct SeqBatch
   int lengths(const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 max_len, u64* bad)
   {
     if(ids) { HIP_TRY(hipMemcpyAsync(d_ids.p, ids, nb * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemsetAsync(d_status.p, 0xFF, sizeof(u64), CTX.stream));                       // SEQ_STATUS_NONE
+    TRY(status.arm());
     LAUNCH("seq_lengths", k_seq_lengths, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), ids_or_null(ids), first_id, nb, (u32)max_len,
-      d_len.as<u32>(), d_status.as<unsigned long long>());
+      d_len.as<u32>(), status.word());
     if(on_host) { HIP_TRY(hipMemcpyAsync(h_len.data(), d_len.p, nb * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
-    TRY(fetch_u64(d_status.as<u64>(), 0));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    *bad = CTX.host_scratch[0];
-    return BWTM_OK;
+    return status.read(bad);
   }
   // the batch's text allocated at its exact size `local`, h_off up (on_host), k_seq_emit (not launched for an empty text); nothing is awaited
   int emit(const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 local)
@@ -64,26 +113,12 @@ extern "C" int bwtm_sequences_extract(const bwtm_index* x, const uint64_t* ids, 
   if(!x || !offsets) { return fail(BWTM_EINVAL, "bwtm_sequences_extract: null argument"); }
   WHOLE_INDEX(x, "bwtm_sequences_extract");
   ENTER(x->ctx);
-  if(max_len == 0) { max_len = SEQ_MAX_LEN_DEFAULT; }
-  if(max_len > SEQ_MAX_LEN_LIMIT) { return fail(BWTM_EINVAL, "bwtm_sequences_extract: max_len %llu is above 2^24", (unsigned long long)max_len); }
+  TRY(check_max_len("bwtm_sequences_extract", &max_len));
   offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  if(!ids)
-  {
-    if(first_id >= x->m || count > x->m - first_id)
-    {
-      return fail(BWTM_EINVAL, "bwtm_sequences_extract: sequence %llu out of range (%llu sequences)", (unsigned long long)std::max<u64>(first_id, x->m), (unsigned long long)x->m);
-    }
-  }
-  else
-  {
-    for(u64 k = 0; k < count; k++)
-    {
-      if(ids[k] >= x->m) { return fail(BWTM_EINVAL, "bwtm_sequences_extract: sequence %llu out of range (%llu sequences)", (unsigned long long)ids[k], (unsigned long long)x->m); }
-    }
-  }
+  TRY(check_sequence_ids("bwtm_sequences_extract", x, ids, first_id, count));
   const bool sizes_only = (!text || capacity == 0);
-  const u64 batch = std::min<u64>(std::min<u64>((u64)g_tune.extract_batch, SEQ_BATCH_LIMIT), count);
+  const u64 batch = std::min<u64>(std::min<u64>((u64)g_tune.extract_batch, WALK_BATCH_LIMIT), count);
   SeqBatch b;
   TRY(b.alloc(batch, ids != nullptr, !sizes_only));
   u64 running = 0;

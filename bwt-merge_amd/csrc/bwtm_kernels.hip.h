@@ -29,16 +29,19 @@
     k_piece_fields     the samples of one piece of a streamed merge, from the encoder's block starts and cum32 (kernels/stream.hip.h)
     k_rank_batch, k_inverse_select_batch, k_extract, k_find_batch
                        BWT::rank / inverse_select / extract, FMI::find  bwt.cpp:318-464, fmi.h:195-221
+    kernels/quad.hip.h (no kernel): four lanes per LF walk -- the record reader (QuadRec, quad_load, quad_symbol, quad_rank,
+                       quad_rank_zero, quad_step) and the bounded walk (quad_walk_to_start) under the three families below, on the quad
+                       primitives of kernels/search_walk.hip.h
     k_seq_lengths, k_seq_emit
-                       sequences by id: the LF walk from the endmarker, four lanes per sequence (kernels/sequences.hip.h; no counterpart
-                       in the reference, the inverse of k_ingest_*)
+                       sequences by id: the LF walk from the endmarker, on the reader of kernels/quad.hip.h (kernels/sequences.hip.h; no
+                       counterpart in the reference, the inverse of k_ingest_*)
     k_locate_build, k_locate_check, k_locate
                        from a BWT position to (sequence id, offset): the same walk from any position, and one table per index that
                        numbers the whole-sequence suffixes (kernels/locate.hip.h; the step the reference's queries leave to the host)
     k_overlap_scan<EMIT>, k_overlap_expand
-                       suffix-prefix overlaps: one backward search per query whose rank(., 0) pairs are intervals of the locator's
-                       table, counted, then emitted longest first and expanded to (id, length) (kernels/overlap.hip.h; the overlap
-                       step of a string-graph assembler, no counterpart in the reference)
+                       suffix-prefix overlaps: one backward search per query (the same reader, two records per step) whose rank(., 0)
+                       pairs are intervals of the locator's table, counted, then emitted longest first and expanded to (id, length)
+                       (kernels/overlap.hip.h; the overlap step of a string-graph assembler, no counterpart in the reference)
 */
 #pragma once
 
@@ -85,6 +88,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/transcode.hip.h"
 #include "kernels/queries.hip.h"
 #include "kernels/search_walk.hip.h"
+#include "kernels/quad.hip.h"
 #include "kernels/sequences.hip.h"
 #include "kernels/locate.hip.h"
 #include "kernels/overlap.hip.h"

@@ -235,8 +235,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_scan_lane(IndexView x
   u64* rec_base, u64* n_hits, u64* hit_base, OverlapRecs recs)
 {
   __shared__ u64 sC[8];
-  if(threadIdx.x < 8) { sC[threadIdx.x] = x.C[threadIdx.x]; }
-  __syncthreads();
+  load_C(sC, x);
   const u64 k = (u64)blockIdx.x * BLOCK_THREADS + threadIdx.x;
   if(k >= count) { return; }
   const u64 begin = offsets[k], end = offsets[k + 1];

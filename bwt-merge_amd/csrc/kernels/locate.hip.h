@@ -1,6 +1,6 @@
 /*
   kernels/locate.hip.h -- from a BWT position back to the collection: the sequence that holds the suffix, and the suffix's offset in it.
-  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/sequences.hip.h whose seq_load / seq_step it uses); gfx950 only.
+  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/quad.hip.h whose record reader and walk it uses); gfx950 only.
 */
 #pragma once
 
@@ -15,39 +15,21 @@
 //
 // The table's entries are u64: 8 bytes per sequence -- 8 GB for 10^9 reads, against about 50 GB of records for 10^11 bases of such reads.
 //
-// Four lanes per walk, as in k_seq_lengths, and the same bounds: a walk ends after max_len steps at the latest and never loads beyond
-// position n - 1, whatever the records hold; a walk still alive after max_len steps, a position >= n or a symbol outside 0..5 sets
-// status = min(status, j) and stores nothing for j.  rank(pos_end, 0) is below n on any records but below m only on sound ones: it is
-// checked against m before it addresses the table.
+// Four lanes per walk and the walk of k_seq_lengths itself (quad_walk_to_start, kernels/quad.hip.h), so the same bounds: a walk ends after
+// max_len steps at the latest and never loads beyond position n - 1, whatever the records hold; a walk still alive after max_len steps, a
+// position >= n or a symbol outside 0..5 sets status = min(status, j) and stores nothing for j.  rank(pos_end, 0) is below n on any
+// records but below m only on sound ones: it is checked against m before it addresses the table.
 
 constexpr u64 LOCATE_UNSET = ~0ull;          // the table's fill value before the build (a pool block is not zero)
 
-// rank(pos, 0) = pos - (the counts of 1..5 before pos), from chunk q of the record of pos and the super-table entries the lane holds
-// (seq_load): every lane adds the five counts of its 32 positions, its slices of the five header fields and its super-table entries.
-__device__ inline u64 quad_rank_zero(uint4 ch, u64 s_q, u64 s_5, u32 q, u64 pos)
-{
-  const u32 jp = (u32)(pos & (REC_POS - 1));
-  u64 part = s_q + (q == 0 ? s_5 : 0);
-#pragma unroll
-  for(u32 c = 1; c < 6; c++) { part += quad_rank_part(ch, q, c, jp); }
-  return pos - quad_sum_u64(part);
-}
-
 // The walk from pos to the start of its sequence: false when it is no walk of a sound index within max_len steps.  On success pos is
-// pos_end, d the number of steps, and k = rank(pos_end, 0) < m.  Quad-uniform.
+// pos_end, d the number of steps, and k = rank(pos_end, 0) < m, taken from the record the walk ended in.  Quad-uniform.
 __device__ inline bool locate_walk(const IndexView& x, const u64* sC, u32 q, u32 max_len, u64& pos, u32& d, u64& k)
 {
-  d = 0;
-  while(true)
-  {
-    if(pos >= x.n) { return false; }
-    uint4 ch; u64 s_q, s_5;
-    seq_load(x, pos, q, ch, s_q, s_5);
-    const u32 c = seq_step(ch, s_q, s_5, q, sC, pos);
-    if(c == 0) { k = quad_rank_zero(ch, s_q, s_5, q, pos); return k < x.m; }
-    if(c > 5 || d == max_len) { return false; }
-    d++;
-  }
+  QuadRec last;
+  if(!quad_walk_to_start(x, sC, q, max_len, pos, d, last)) { return false; }
+  k = quad_rank_zero(last, q, pos);
+  return k < x.m;
 }
 
 // table[rank(pos_end, 0)] = id for the sequences first .. first + count - 1.  Distinct sequences of a sound index end at distinct
@@ -55,8 +37,7 @@ __device__ inline bool locate_walk(const IndexView& x, const u64* sC, u32 q, u32
 __global__ void __launch_bounds__(BLOCK_THREADS) k_locate_build(IndexView x, u64 first, u64 count, u32 max_len, u64* table, unsigned long long* status)
 {
   __shared__ u64 sC[8];
-  if(threadIdx.x < 8) { sC[threadIdx.x] = x.C[threadIdx.x]; }
-  __syncthreads();
+  load_C(sC, x);
   const u32 q = threadIdx.x & 3;
   const u64 j = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 2;
   if(j >= count) { return; }
@@ -86,8 +67,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_locate(IndexView x, const u64
   const u64* range_first_hit, u64 nranges, u64 count, u32 max_len, u64* ids, u64* offs, unsigned long long* status)
 {
   __shared__ u64 sC[8];
-  if(threadIdx.x < 8) { sC[threadIdx.x] = x.C[threadIdx.x]; }
-  __syncthreads();
+  load_C(sC, x);
   const u32 q = threadIdx.x & 3;
   const u64 h = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 2;
   if(h >= count) { return; }
@@ -95,13 +75,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_locate(IndexView x, const u64
   if(positions) { pos = positions[h]; }
   else
   {
-    u64 lo = 0, hi = nranges;                                    // range_first_hit[lo] <= h < range_first_hit[hi]
-    while(hi - lo > 1)
-    {
-      const u64 mid = lo + (hi - lo) / 2;
-      if(range_first_hit[mid] <= h) { lo = mid; } else { hi = mid; }
-    }
-    pos = range_start[lo] + (h - range_first_hit[lo]);
+    const u64 r = last_at_or_below(range_first_hit, nranges, h);
+    pos = range_start[r] + (h - range_first_hit[r]);
   }
   u64 k = 0, id = 0;
   u32 d = 0;

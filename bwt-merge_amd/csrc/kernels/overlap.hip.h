@@ -1,6 +1,6 @@
 /*
   kernels/overlap.hip.h -- suffix-prefix overlaps: for a query Q, the sequences whose prefix equals a suffix of Q.
-  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/locate.hip.h whose table and quad_rank_zero it uses); gfx950 only.
+  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/locate.hip.h whose table it uses); gfx950 only.
 */
 #pragma once
 
@@ -13,11 +13,10 @@
 // So the hits of length l are table[z] for z in [z0, z1), in ascending BWT position of the target, and no walk is needed at all: one
 // backward search per query -- the two rank positions of every step serve both the next LF step and the interval -- plus table look-ups.
 //
-// FOUR lanes per query, the quad loader of kernels/sequences.hip.h twice per step: lane q loads chunk q of the record of sp AND of the
-// record of ep + 1, and its super-table entries of both, all requested together; every lane counts in its 32 positions of either record and
-// the quad butterflies add the pieces.  A quad is uniform in control flow (its lanes hold the same sp, ep, symbol and length); quads that
-// have finished, and the idle quads behind `count`, have left the loop and feed nobody.  The search never loads beyond position n - 1:
-// rank(n, .) is taken from C.
+// FOUR lanes per query, the record reader of kernels/quad.hip.h twice per step: the records of sp AND of ep + 1 are requested together and
+// pinned together (the two-record quad_load), and both ranks of either come from those registers.  A quad is uniform in
+// control flow (its lanes hold the same sp, ep, symbol and length); quads that have finished, and the idle quads behind `count`, have
+// left the loop and feed nobody.  The search never loads beyond position n - 1: rank(n, .) is taken from C.
 //
 // The search finds the lengths ascending, the output wants them descending (longest overlap first).  Two passes over the same text: the
 // COUNT pass stores, per query, the number of non-empty intervals and of hits (both before max_hits) and the hits kept; two scans on the
@@ -35,27 +34,6 @@ struct OverlapRecs
   u64* len;        // the overlap's length
 };
 
-// Chunk q of the records of pa and pb and the lane's super-table entries of both, all requested together (seq_load twice would pin the
-// first record's values before the second record is requested).
-__device__ inline void overlap_load(const IndexView& x, u64 pa, u64 pb, u32 q, uint4& ca, u64& sa_q, u64& sa_5, uint4& cb, u64& sb_q, u64& sb_5)
-{
-  ca = x.recs[4 * (pa >> REC_SHIFT) + q];
-  cb = x.recs[4 * (pb >> REC_SHIFT) + q];
-  const u64* sa = x.sup + (pa >> SUPER_SHIFT) * SUP_STRIDE;
-  const u64* sb = x.sup + (pb >> SUPER_SHIFT) * SUP_STRIDE;
-  sa_q = sa[1 + q]; sa_5 = sa[5];
-  sb_q = sb[1 + q]; sb_5 = sb[5];
-  asm volatile("" : "+v"(ca.x), "+v"(ca.y), "+v"(ca.z), "+v"(ca.w), "+v"(sa_q), "+v"(sa_5), "+v"(cb.x), "+v"(cb.y), "+v"(cb.z), "+v"(cb.w), "+v"(sb_q), "+v"(sb_5));
-}
-
-// rank(pos, c) for c in 1..5 from what overlap_load left in the quad.
-__device__ inline u64 quad_rank_sym(uint4 ch, u64 s_q, u64 s_5, u32 q, u32 c, u64 pos)
-{
-  const u32 jp = (u32)(pos & (REC_POS - 1));
-  const u64 part = (u64)quad_rank_part(ch, q, c, jp) + (c == q + 1 ? s_q : 0) + ((q == 0 && c == 5) ? s_5 : 0);
-  return quad_sum_u64(part);
-}
-
 // Query k = text[offsets[k] .. offsets[k + 1]), comp values 1..5 (anything else ends the search there: nothing matches it).
 // EMIT == false: rec_base[k] = the query's intervals, n_hits[k] = its hits, hit_base[k] = the hits kept of them; the generic scan then turns
 // rec_base[0 .. count] and hit_base[0 .. count] in place into the first record and the first hit slot of every query.
@@ -65,8 +43,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_scan(IndexView x, con
   u64* rec_base, u64* n_hits, u64* hit_base, OverlapRecs recs)
 {
   __shared__ u64 sC[8];
-  if(threadIdx.x < 8) { sC[threadIdx.x] = x.C[threadIdx.x]; }
-  __syncthreads();
+  load_C(sC, x);
   const u32 q = threadIdx.x & 3;
   const u64 k = ((u64)blockIdx.x * BLOCK_THREADS + threadIdx.x) >> 2;
   if(k >= count) { return; }
@@ -89,12 +66,12 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_scan(IndexView x, con
       const bool at_end = (e1 == x.n);
       const u64 pe = (at_end ? e1 - 1 : e1);
       const u32 c = (pos > begin ? (u32)text[pos - 1] : 0u);                // the next symbol, 0: none
-      uint4 ca, cb; u64 sa_q, sa_5, sb_q, sb_5;
-      overlap_load(x, sp, pe, q, ca, sa_q, sa_5, cb, sb_q, sb_5);
+      QuadRec ra, rb;
+      quad_load(x, sp, pe, q, ra, rb);
       if(len >= min_overlap)
       {
-        const u64 z0 = quad_rank_zero(ca, sa_q, sa_5, q, sp);
-        const u64 z1 = (at_end ? sC[1] - sC[0] : quad_rank_zero(cb, sb_q, sb_5, q, e1));
+        const u64 z0 = quad_rank_zero(ra, q, sp);
+        const u64 z1 = (at_end ? sC[1] - sC[0] : quad_rank_zero(rb, q, e1));
         if(z1 > z0)
         {
           const u64 cnt = z1 - z0;
@@ -115,9 +92,8 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_scan(IndexView x, con
         }
       }
       if(c < 1 || c > 5) { break; }
-      const u64 ra = quad_rank_sym(ca, sa_q, sa_5, q, c, sp);
-      const u64 rb = (at_end ? sC[c + 1] - sC[c] : quad_rank_sym(cb, sb_q, sb_5, q, c, e1));
-      sp = sC[c] + ra; e1 = sC[c] + rb;
+      sp = sC[c] + quad_rank(ra, q, c, sp);
+      e1 = sC[c] + (at_end ? sC[c + 1] - sC[c] : quad_rank(rb, q, c, e1));
       pos--; len++;
     }
   }
@@ -145,12 +121,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_overlap_expand(const u64* tab
   const u64 j = (u64)blockIdx.x * BLOCK_THREADS + threadIdx.x;
   if(j >= count) { return; }
   const u64 h = first_hit + j;
-  u64 lo = 0, hi = nrecs;                                        // first[lo] <= h < first[hi]
-  while(hi - lo > 1)
-  {
-    const u64 mid = lo + (hi - lo) / 2;
-    if(recs.first[mid] <= h) { lo = mid; } else { hi = mid; }
-  }
+  const u64 lo = last_at_or_below(recs.first, nrecs, h);
   const u64 e = h - recs.first[lo];
   const u64 z = recs.z0[lo] + e;
   bool ok = (e < recs.cnt[lo] && z >= e && z < m);
