@@ -1317,6 +1317,17 @@ def frontier_step_forms():
     return tuple(int(v) for v in n)
 
 
+def transcode_forms():
+    """Launches of k_build_recs / k_build_recs_chunk since the last profile_reset by instantiation, 16 counts: index 8 * chunk + 2 * w +
+    uniform, w = 0 / 1 / 2 for the windows of 8192 / 16384 / 32768 positions and 3 for 32768 with the cooperative fill; counted whether or
+    not profiling is enabled."""
+    f = lib().bwtm_transcode_forms          # bound on first use, as frontier_step_forms is
+    f.restype = C.c_int; f.argtypes = [p_u64]
+    n = (u64 * 16)()
+    check(f(n))
+    return tuple(int(v) for v in n)
+
+
 def profile_read():
     """{kernel name: (total_ms, launches)} since the last reset."""
     cap = 64

@@ -74,6 +74,7 @@ struct bwtm_context
   // two-launch form.  (A device that is shared with other processes delays such a kernel, it cannot deadlock it: the others' kernels end.)
   u64 scan1_tiles = 0, pull_scan1_tiles = 0;
   u64 step_forms[3] = {0, 0, 0};           // k_frontier_step launches per form of the coordinates (REL) since the last bwtm_profile_reset
+  u64 transcode_forms[16] = {};            // k_build_recs / k_build_recs_chunk launches per instantiation (transcode_form) since the last bwtm_profile_reset
 };
 
 namespace
@@ -297,6 +298,12 @@ void profile_collect()
   CTX.step_forms[REL]++; \
   if(g_tune.frontier_stage_out) { LAUNCH(name, (k_frontier_step<Rel<REL>, EMIT, HI, true>), grid, FR_BLOCK, __VA_ARGS__); } \
   else { LAUNCH(name, (k_frontier_step<Rel<REL>, EMIT, HI, false>), grid, FR_BLOCK, __VA_ARGS__); } } while(0)
+// Index of an instantiation of k_build_recs<W, WAVES, FILL, UNIFORM> (chunk = 0) or k_build_recs_chunk (chunk = 1) in CTX.transcode_forms
+// (bwtm_transcode_forms): 8 chunk + 2 w + uniform, w = 0 / 1 / 2 for the windows of 8192 / 16384 / 32768 positions, 3 for 32768 with FILL
+constexpr int transcode_form(int chunk, u32 window, bool fill, bool uniform)
+{
+  return 8 * chunk + 2 * (window == 8192 ? 0 : (window == 16384 ? 1 : (fill ? 3 : 2))) + (uniform ? 1 : 0);
+}
 // The plain search: rel = 0 absolute coordinates, 1 = absolute in and class-relative out (the first step), 2 = class-relative (no high bytes: HI is not read)
 #define LAUNCH_STEP_REL(name, EMIT, HI, rel, grid, ...) do { \
   if((rel) == 2) { LAUNCH_STEP_FORM(name, EMIT, false, 2, grid, __VA_ARGS__); } \
@@ -862,6 +869,15 @@ extern "C" int bwtm_profile_reset(void)
   profile_collect();
   CTX.totals.clear(); CTX.order.clear();
   for(int k = 0; k < 3; k++) { CTX.step_forms[k] = 0; }
+  for(int k = 0; k < 16; k++) { CTX.transcode_forms[k] = 0; }
+  return BWTM_OK;
+}
+
+extern "C" int bwtm_transcode_forms(uint64_t launches[16])
+{
+  if(!launches) { return fail(BWTM_EINVAL, "bwtm_transcode_forms: null argument"); }
+  ENTER(nullptr);
+  for(int k = 0; k < 16; k++) { launches[k] = CTX.transcode_forms[k]; }
   return BWTM_OK;
 }
 

@@ -227,9 +227,10 @@ int build_records(bwtm_index* x, u64 held, u64 n_end, uint4* recs, u64 nrecs)
   const u64 gstride = x->ngroups + 1;
   const u64 per_group = held / x->ngroups;
   const bool long_runs = (x->nblocks > 0 && held / x->nblocks > 400);        // > ~6 positions per byte: cooperative fill of long runs pays
-#define BUILD_RECS(W, WAVES, FILL, UNIFORM) LAUNCH("build_recs", (k_build_recs<W, WAVES, FILL, UNIFORM>), div_up(x->ngroups, WAVES), WAVES * WAVE, \
+#define BUILD_RECS(W, WAVES, FILL, UNIFORM) do { CTX.transcode_forms[transcode_form(0, W, FILL, UNIFORM)]++; \
+    LAUNCH("build_recs", (k_build_recs<W, WAVES, FILL, UNIFORM>), div_up(x->ngroups, WAVES), WAVES * WAVE, \
     x->native_bytes(), x->nbytes, x->blen.as<const u64>(), x->block_start.as<u64>(), x->gcum.as<const u64>(), gstride, x->nblocks, x->ngroups, n_end, \
-    x->sup.as<const u64>(), recs, nrecs)
+    x->sup.as<const u64>(), recs, nrecs); } while(0)
   const u64 window = (g_tune.recs_window != 0 ? (u64)g_tune.recs_window : (per_group <= 6500 ? 8192 : (per_group <= 14000 ? 16384 : 32768)));
   // the straight-line deposit for streams of longer runs (kernels/transcode.hip.h): from ~3.5 positions per byte on
   const bool uniform = (g_tune.recs_uniform != 0 ? g_tune.recs_uniform > 0 : window == 32768);

@@ -113,9 +113,10 @@ struct ChunkedUpload
       LAUNCH("build_sup", k_build_sup_chunk, div_up(x->nsup * WAVE, BLOCK_THREADS), BLOCK_THREADS,
         (const u8*)dst, local_bytes, blen.as<const u64>(), gtab.as<const u64>(), gstride, local_blocks, ngl, bases, x->sup.as<u64>(), x->nsup,
         (const u64*)state_p, last);
-#define BUILD_RECS_CHUNK(W, WAVES, FILL, UNIFORM) LAUNCH("build_recs", (k_build_recs_chunk<W, WAVES, FILL, UNIFORM>), div_up(ngl, WAVES), WAVES * WAVE, \
+#define BUILD_RECS_CHUNK(W, WAVES, FILL, UNIFORM) do { CTX.transcode_forms[transcode_form(1, W, FILL, UNIFORM)]++; \
+        LAUNCH("build_recs", (k_build_recs_chunk<W, WAVES, FILL, UNIFORM>), div_up(ngl, WAVES), WAVES * WAVE, \
         (const u8*)dst, local_bytes, blen.as<const u64>(), gtab.as<const u64>(), gstride, local_blocks, ngl, bases, \
-        x->sup.as<const u64>(), x->recs.as<uint4>(), x->nrecs, (const u64*)state_p, last)
+        x->sup.as<const u64>(), x->recs.as<uint4>(), x->nrecs, (const u64*)state_p, last); } while(0)
       if(window == 8192) { if(uniform) { BUILD_RECS_CHUNK(8192, 4, false, true); } else { BUILD_RECS_CHUNK(8192, 4, false, false); } }
       else if(window == 16384) { if(uniform) { BUILD_RECS_CHUNK(16384, 4, false, true); } else { BUILD_RECS_CHUNK(16384, 4, false, false); } }
       else if(!long_runs) { if(uniform) { BUILD_RECS_CHUNK(32768, 2, false, true); } else { BUILD_RECS_CHUNK(32768, 2, false, false); } }

@@ -592,6 +592,11 @@ int bwtm_profile_reset(void);
    form of the frontier's coordinates: [0] absolute in and out, [1] absolute in and class-relative out (the first step of a search that
    takes the class-relative form), [2] class-relative in and out (bwtm_tune "frontier_rel"). */
 int bwtm_frontier_step_forms(uint64_t launches[3]);
+/* Launches of the kernel that builds an index's records from its native stream since the last bwtm_profile_reset (counted whether or
+   not profiling is enabled), by instantiation: index 8 * chunk + 2 * w + uniform.  chunk: 0 the one-shot upload, 1 the chunked upload;
+   w: the LDS window, 0 = 8192 positions, 1 = 16384, 2 = 32768, 3 = 32768 with the cooperative fill of long runs; uniform: 1 = the
+   straight-line deposit (bwtm_tune "recs_window", "recs_uniform"; otherwise by the stream's average density). */
+int bwtm_transcode_forms(uint64_t launches[16]);
 /* Per-kernel totals since the last reset: returns the number of distinct kernels; fills up to
    `capacity` entries.  names[k] points to a static string. */
 int bwtm_profile_read(const char** names, double* total_ms, uint64_t* launches, int capacity);

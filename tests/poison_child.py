@@ -286,9 +286,21 @@ def family_exact_merges(pkg, orc):
         pkg.trim()
 
 
+def family_transcode_forms(pkg, orc):
+    """k_build_recs and k_build_recs_chunk forced onto streams they are not chosen for (tests/test_gpu_transcode_forms.py): the smallest and
+    the largest window, both deposits, through the one-shot and the chunked upload.  A small window over a giant group reads more of blen,
+    the group tables and the records per wave than any other case; the form counter shows that the setting took effect."""
+    from test_gpu_transcode_forms import case, check_setting
+    for name in ("giants_with_dense", "edges_8192"):
+        c = case(orc, name)
+        for window, uniform in ((8192, -1), (8192, 1), (32768, -1), (32768, 1)):
+            for entry in ("upload", "streamed_1"):
+                check_setting(pkg, c, window, uniform, entry)
+
+
 FAMILIES = {"reads": family_reads, "odd": family_odd, "runs": family_runs, "encoder": family_encoder, "epochs": family_epochs, "host": family_host,
             "slices": family_slices, "parts": family_parts, "ingest": family_ingest, "exact_builders": family_exact_builders,
-            "exact_merges": family_exact_merges}
+            "exact_merges": family_exact_merges, "transcode_forms": family_transcode_forms}
 
 
 def main(family):

@@ -25,6 +25,9 @@ def test_every_declared_function_is_exported_and_bound(bwtm):
     assert not missing, missing
     for n, _, _ in bwtm.capi.SYMBOLS:
         assert n in names, "capi.py binds %s, which include/bwtm.h does not declare" % n
+    # the two launch-form counters are bound on first use, not with SYMBOLS: declared, exported, and reachable through the package
+    for n in ("bwtm_frontier_step_forms", "bwtm_transcode_forms"):
+        assert n in names and n not in bound and callable(getattr(bwtm, n[len("bwtm_"):]))
 
 
 def test_experimental_header_matches_the_experimental_library(bwtm):

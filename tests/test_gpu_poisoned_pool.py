@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 CHILD = os.path.join(ROOT, "tests", "poison_child.py")
 POOLS = {"default_pool": {}, "mapped_2mib": {"BWTM_POOL_VMM_CHUNK": "2097152", "BWTM_POOL_VMM_MIN": "65536"}}
-FAMILIES = ["reads", "odd", "runs", "encoder", "epochs", "host", "slices", "parts", "ingest"]
+FAMILIES = ["reads", "odd", "runs", "encoder", "epochs", "host", "slices", "parts", "ingest", "transcode_forms"]
 MAPPED_TOO = ["reads", "odd", "runs", "parts"]
 CASES = [(f, w, "default_pool") for f in FAMILIES for w in ("0x00000000", "0xA5A5A5A5")] + [(f, w, "mapped_2mib") for f in MAPPED_TOO for w in ("0x00000000", "0xA5A5A5A5")]
 
