@@ -145,6 +145,14 @@ SYMBOLS = [
     ("bwtm_locate_ranges", C.c_int, [vp, p_u64, p_u64, u64, u64, p_u64, p_u64, p_u64, u64]),
     ("bwtm_overlap_batch", C.c_int, [vp, p_u8, p_u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
     ("bwtm_overlap_sequences", C.c_int, [vp, p_u64, u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
+    ("bwtm_kmers_create", C.c_int, [vp, C.c_uint32, C.c_uint32, u64, C.POINTER(vp)]),
+    ("bwtm_kmers_free", None, [vp]),
+    ("bwtm_kmers_distinct", u64, [vp]),
+    ("bwtm_kmers_total", u64, [vp]),
+    ("bwtm_kmers_bytes", u64, [vp]),
+    ("bwtm_kmers_levels", C.c_int, [vp, p_u64]),
+    ("bwtm_kmers_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64]),
+    ("bwtm_kmers_histogram", C.c_int, [vp, u64, p_u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -782,6 +790,79 @@ class Index:
     def locator(self, max_len=0):
         """The table that turns BWT positions into (sequence id, offset) (bwtm_locator_create).  The locator borrows this index."""
         return Locator(self, max_len)
+
+    def kmers(self, k, skip=5, min_count=1):
+        """The distinct k-mers of the collection with their counts and BWT ranges (bwtm_kmers_create); skip = the comp of N."""
+        return Kmers(self, k, skip, min_count)
+
+
+KMER_MAX_K = 32
+
+
+def kmer_comps(skip):
+    """The comp values of the k-mer alphabet: 1..5 without skip, ascending."""
+    return np.array([c for c in range(1, 6) if c != int(skip)], dtype=np.uint8)
+
+
+def decode_kmers(codes, k, skip):
+    """Codes of k-mers (2 bits per symbol, the first symbol in the highest used bits) -> rows of k comp values."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint64)
+    shifts = (2 * np.arange(int(k) - 1, -1, -1)).astype(np.uint64)
+    return kmer_comps(skip)[((codes[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.int64)]
+
+
+class Kmers:
+    """The kept k-mers of an index in ascending order, on the device (handle on bwtm_kmers).  It does not borrow the index."""
+
+    def __init__(self, index, k, skip=5, min_count=1):
+        out = vp()
+        check(lib().bwtm_kmers_create(index.h, int(k), int(skip), int(min_count), C.byref(out)))
+        self.h = out
+        self.k, self.skip = int(k), int(skip)
+
+    distinct = property(lambda s: int(lib().bwtm_kmers_distinct(s.h)))
+    total = property(lambda s: int(lib().bwtm_kmers_total(s.h)))
+    nbytes = property(lambda s: int(lib().bwtm_kmers_bytes(s.h)))
+
+    def free(self):
+        if self.h:
+            lib().bwtm_kmers_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h:
+            raise BwtmError("the k-mers have been freed")
+
+    def levels(self):
+        """nodes[t] = distinct (t + 1)-mers with count >= min_count, t < k."""
+        self._live()
+        nodes = np.zeros(KMER_MAX_K, dtype=np.uint64)
+        check(lib().bwtm_kmers_levels(self.h, nodes.ctypes.data_as(p_u64)))
+        return nodes[: self.k]
+
+    def download(self, first=0, count=None):
+        """(codes, counts, sp) of the entries [first, first + count) (count=None: up to the last one)."""
+        self._live()
+        if count is None:
+            count = max(self.distinct - int(first), 0)
+        if int(first) + int(count) > self.distinct:                      # the library says so, before arrays of that size are made
+            check(lib().bwtm_kmers_download(self.h, int(first), int(count), None, None, None))
+        codes, counts, sp = (np.zeros(int(count), dtype=np.uint64) for _ in range(3))
+        check(lib().bwtm_kmers_download(self.h, int(first), int(count), codes.ctypes.data_as(p_u64), counts.ctypes.data_as(p_u64), sp.ctypes.data_as(p_u64)))
+        return codes, counts, sp
+
+    def histogram(self, bins):
+        """hist[j] = kept k-mers of count j, the last bin those of count >= bins - 1."""
+        self._live()
+        hist = np.zeros(max(int(bins), 0), dtype=np.uint64)
+        check(lib().bwtm_kmers_histogram(self.h, int(bins), hist.ctypes.data_as(p_u64)))
+        return hist
 
 
 class Locator:

@@ -120,6 +120,7 @@ struct Tuning
   long long walk_variant = 0;    // 1 = LDS-transposed one chain per lane
   long long scatter_kernel = 0;  // 1 = direct scattered stores in level 2 of the partition (first version)
   long long overlap_kernel = 0;  // 0 = four lanes per query (default), 1 = one lane per query (k_find_batch's shape): the same results
+  long long kmers_kernel = 0;    // 0 = one lane per trie node (default), 1 = four lanes per node on the record reader of kernels/quad.hip.h: the same results
 #endif
 };
 Tuning g_tune;
@@ -745,6 +746,7 @@ int tune_set(const char* key, long long value)
   else if(k == "walk_variant") { g_tune.walk_variant = value; }
   else if(k == "scatter_kernel") { g_tune.scatter_kernel = value; }
   else if(k == "overlap_kernel") { g_tune.overlap_kernel = (value == 1 ? 1 : 0); }
+  else if(k == "kmers_kernel") { g_tune.kmers_kernel = (value == 1 ? 1 : 0); }
 #endif
   else { return fail(BWTM_EINVAL, "bwtm_tune: unknown key %s", key); }
   return BWTM_OK;

@@ -42,6 +42,10 @@
                        suffix-prefix overlaps: one backward search per query (the same reader, two records per step) whose rank(., 0)
                        pairs are intervals of the locator's table, counted, then emitted longest first and expanded to (id, length)
                        (kernels/overlap.hip.h; the overlap step of a string-graph assembler, no counterpart in the reference)
+    k_kmer_level<QUAD, EMIT>, k_kmer_sum, k_kmer_hist
+                       the distinct k-mers with their counts: the suffix trie down to depth k, level by level, every level the stable
+                       split by symbol of the one before (count pass, scan, expand-and-scatter pass), and the spectrum of the result
+                       (kernels/kmers.hip.h; no counterpart in the reference)
 */
 #pragma once
 
@@ -92,6 +96,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/sequences.hip.h"
 #include "kernels/locate.hip.h"
 #include "kernels/overlap.hip.h"
+#include "kernels/kmers.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

@@ -233,6 +233,55 @@ private:
   bwtm_locator* handle = nullptr;
 };
 
+// The distinct k-mers of an FMI's collection with their counts and ranges, ascending, on the device (bwtm_kmers_create): k-mers over the
+// four comp values 1..5 other than `skip` (the comp of N), 1 <= k <= 32, kept when they occur at least min_count times.  The index goes to
+// the device if it is not there, and stays; the result does not borrow it.
+class Kmers
+{
+public:
+  typedef BWT::size_type size_type;
+
+  Kmers(const FMI& fmi, size_type k, size_type skip, size_type min_count = 1) : k(k), skip(skip)
+  {
+    gpuCheck(bwtm_kmers_create(fmi.bwt.onDevice(fmi.alpha.C), (uint32_t)std::min<size_type>(k, ~(uint32_t)0), (uint32_t)std::min<size_type>(skip, ~(uint32_t)0), min_count,
+      &this->handle), "Kmers::Kmers()");
+  }
+  ~Kmers() { bwtm_kmers_free(this->handle); }
+  Kmers(const Kmers&) = delete; Kmers& operator=(const Kmers&) = delete;
+
+  size_type distinct() const { return bwtm_kmers_distinct(this->handle); }
+  size_type total() const { return bwtm_kmers_total(this->handle); }
+  size_type bytes() const { return bwtm_kmers_bytes(this->handle); }
+
+  // The entries [first, first + count) in ascending order; sp may be null.
+  void download(size_type first, size_type count, std::vector<uint64_t>& codes, std::vector<uint64_t>& counts, std::vector<uint64_t>* sp = nullptr) const
+  {
+    codes.resize(count); counts.resize(count);
+    if(sp) { sp->resize(count); }
+    gpuCheck(bwtm_kmers_download(this->handle, first, count, codes.data(), counts.data(), (sp ? sp->data() : nullptr)), "Kmers::download()");
+  }
+
+  // hist[j] = kept k-mers of count j, the last bin those of count >= bins - 1.
+  std::vector<uint64_t> histogram(size_type bins) const
+  {
+    std::vector<uint64_t> hist(bins, 0);
+    gpuCheck(bwtm_kmers_histogram(this->handle, bins, hist.data()), "Kmers::histogram()");
+    return hist;
+  }
+
+  // Symbol j (0 = first) of a code as its comp value.
+  byte_type comp(uint64_t code, size_type j) const
+  {
+    const size_type rank = (code >> (2 * (k - 1 - j))) & 3;
+    return (byte_type)(rank + 1 + (rank + 1 >= skip ? 1 : 0));
+  }
+
+  const size_type k, skip;
+
+private:
+  bwtm_kmers* handle = nullptr;
+};
+
 // Search phase (buildRA, reference fmi.cpp:272-334) as a free function: makes sure a and b are on the device and
 // fills a device rank array; parameters.sequence_blocks splits the sequences of b.
 inline void buildRA(const FMI& a, const FMI& b, const MergeParameters& parameters, RankArray& ra)

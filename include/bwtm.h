@@ -225,6 +225,36 @@ int bwtm_overlap_sequences(const bwtm_locator* locator, const uint64_t* ids, uin
                            uint64_t min_overlap, uint64_t max_hits, uint64_t* hit_offsets,
                            uint64_t* out_ids, uint64_t* out_lengths, uint64_t capacity);
 
+/* The distinct k-mers of the collection with their counts: the question an assembler or a QC step asks before it computes overlaps
+   (coverage peak, genome size, the solid / weak threshold of error correction).  `skip` is one comp value 1..5, the comp of N (5 in
+   the default alphabet, 4 in the sorted one); the four other comp values, ranked 0..3 in ascending order, are the k-mer alphabet.
+   A k-mer (1 <= k <= 32) is a string of k such symbols; its COUNT is the number of pairs (i, o) with S_i[o .. o + k) equal to it
+   (occurrences inside sequences: nothing spans an endmarker, a sequence shorter than k contributes nothing); its CODE holds 2 bits
+   per symbol, the first symbol in the highest used bits, so codes compare like the strings; its RANGE is the closed BWT range
+   [sp, sp + count - 1] of the suffixes that start with it, the one bwtm_find_batch returns for it and bwtm_locate_ranges takes.
+   min_count (0 is taken as 1) keeps the k-mers whose count is at least min_count.  The result lists the kept k-mers in ascending
+   code order, which is ascending sp order as well, and lives on the device; it does not borrow the index once created.
+   The suffix trie is expanded level by level on the device: 2 (k - 1) launches over frontiers of 24 bytes per node and one small
+   read-back per level.  Works on any whole index (uploaded, merged, built; records and super table suffice), not on a window.
+   Device memory of the call beyond the index, with P = the largest entry of bwtm_kmers_levels: at most 240 P + 2^20 bytes while
+   every block stays below 512 MiB (api/kmers.hip.h derives it); the handle keeps 24 bytes per kept k-mer.  A result that does not
+   fit the device is BWTM_ENOMEM: raise min_count or lower k.
+   BWTM_EINVAL, bwtm_last_error() saying which: k == 0 or k > 32, skip outside 1..5, a window of an index, first + count beyond
+   bwtm_kmers_distinct (a sum that wraps included), bins < 2. */
+typedef struct bwtm_kmers bwtm_kmers;
+int bwtm_kmers_create(const bwtm_index* index, uint32_t k, uint32_t skip, uint64_t min_count, bwtm_kmers** out);
+void bwtm_kmers_free(bwtm_kmers* kmers);
+uint64_t bwtm_kmers_distinct(const bwtm_kmers* kmers);             /* kept k-mers */
+uint64_t bwtm_kmers_total(const bwtm_kmers* kmers);                /* sum of their counts */
+uint64_t bwtm_kmers_bytes(const bwtm_kmers* kmers);                /* device bytes the handle holds */
+/* nodes[t] (t = 0 .. k - 1) = number of distinct (t + 1)-mers with count >= min_count: the frontier after each level; 0 behind k */
+int bwtm_kmers_levels(const bwtm_kmers* kmers, uint64_t nodes[32]);
+/* entries [first, first + count) in code order; any of the three output arrays may be NULL */
+int bwtm_kmers_download(const bwtm_kmers* kmers, uint64_t first, uint64_t count,
+                        uint64_t* codes, uint64_t* counts, uint64_t* sp);
+/* hist[j] = number of kept k-mers of count j for j < bins - 1; hist[bins - 1] = those of count >= bins - 1; bins >= 2 */
+int bwtm_kmers_histogram(const bwtm_kmers* kmers, uint64_t bins, uint64_t* hist);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
