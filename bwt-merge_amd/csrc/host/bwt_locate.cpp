@@ -5,6 +5,9 @@
   line, and mapped exactly as `bwt_merge -v` reads them.  The output holds one line per hit,
       pattern_number <TAB> sequence <TAB> offset        (all 0-based)
   in the order of the patterns and, within a pattern, sorted by (sequence, offset): two runs compare with cmp.
+  With -d N the search allows up to N substitutions (bwtm_find_approx_batch: no indels, no reverse complements) and every line gains a
+  fourth column, the number of places in which the occurrence differs from the pattern; -x then bounds the occurrences written per
+  matched string.  Without -d the output is what it always was.
   Sequence k of an index built by bwt_ingest, or merged from such indexes by bwt_merge, is read k of the input(s) in order.
 */
 #include <unistd.h>
@@ -22,7 +25,9 @@ static void printUsage()
   std::cerr << "  -g N           Use GPU N (default: 0)" << std::endl;
   std::cerr << "  -i format      Read the input in the given format (default: native)" << std::endl;
   std::cerr << "  -m N           Longest sequence the input may hold (default: 65536, at most 16777216)" << std::endl;
-  std::cerr << "  -x N           Write at most N hits per pattern: the first N positions of its range (default: all)" << std::endl << std::endl;
+  std::cerr << "  -x N           Write at most N hits per pattern: the first N positions of its range (default: all)" << std::endl;
+  std::cerr << "  -d N           Allow up to N substitutions, 0 to 8, and write the mismatches of every hit as a fourth column;" << std::endl;
+  std::cerr << "                 -x then applies to every matched string (default: exact search, three columns)" << std::endl << std::endl;
   printFormats(std::cerr);
 }
 
@@ -44,8 +49,9 @@ int main(int argc, char** argv)
 
   int device = 0;
   std::string input_tag = NativeFormat::tag();
-  size_type max_len = 0, max_hits = 0;
-  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:")) != -1; )
+  size_type max_len = 0, max_hits = 0, mismatches = 0;
+  bool approx = false;
+  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:d:")) != -1; )
   {
     switch(c)
     {
@@ -56,6 +62,10 @@ int main(int argc, char** argv)
       break;
     case 'm': max_len = std::stoull(optarg); break;
     case 'x': max_hits = std::stoull(optarg); break;
+    case 'd':
+      approx = true; mismatches = std::stoull(optarg);
+      if(mismatches > 8) { std::cerr << "bwt_locate: -d takes 0 to 8 mismatches" << std::endl; std::exit(EXIT_FAILURE); }
+      break;
     default: std::exit(EXIT_FAILURE);
     }
   }
@@ -63,7 +73,9 @@ int main(int argc, char** argv)
   std::string input_name = argv[optind], pattern_name = argv[optind + 1], output_name = argv[optind + 2];
   std::cout << "Input:    " << input_name << " (" << input_tag << ")" << std::endl;
   std::cout << "Patterns: " << pattern_name << std::endl;
-  std::cout << "Output:   " << output_name << " (pattern, sequence, offset)" << std::endl << std::endl;
+  std::cout << "Output:   " << output_name << (approx ? " (pattern, sequence, offset, mismatches)" : " (pattern, sequence, offset)") << std::endl;
+  if(approx) { std::cout << "Search:   up to " << mismatches << " substitutions" << std::endl; }
+  std::cout << std::endl;
 
   double start = readTimer();
   gpuCheck(bwtm_init(device), "bwt_locate");
@@ -85,27 +97,62 @@ int main(int argc, char** argv)
       for(char ch : patterns[k]) { text.push_back(fmi.alpha.char2comp[(byte_type)ch]); }
       offsets[k + 1] = text.size();
     }
-    bwtm_index* ix = fmi.bwt.onDevice(fmi.alpha.C);
-    gpuCheck(bwtm_find_batch(ix, text.data(), offsets.data(), patterns.size(), sp.data(), ep.data()), "bwt_locate");
-    std::vector<range_type> ranges(patterns.size());
-    for(size_type k = 0; k < patterns.size(); k++) { ranges[k] = range_type(sp[k], ep[k]); }
-
-    Locator locator(fmi, max_len);
-    std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
-    locator.locate(ranges, hit_offsets, hits, max_hits);
-    total = hits.size();
-    std::string lines;
-    for(size_type k = 0; k < patterns.size(); k++)
+    if(approx)
     {
-      if(hit_offsets[k + 1] == hit_offsets[k]) { continue; }
-      found++;
-      std::sort(hits.begin() + hit_offsets[k], hits.begin() + hit_offsets[k + 1]);
-      lines.clear();
-      for(size_type h = hit_offsets[k]; h < hit_offsets[k + 1]; h++)
+      // every matched string of a pattern is a range of its own: located like the others, its mismatches written with every occurrence
+      std::vector<size_type> string_offsets; std::vector<FMI::ApproxHit> strings;
+      fmi.findApprox(text, offsets, mismatches, string_offsets, strings);
+      std::vector<range_type> ranges(strings.size());
+      for(size_type s = 0; s < strings.size(); s++) { ranges[s] = strings[s].range; }
+      Locator locator(fmi, max_len);
+      std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
+      locator.locate(ranges, hit_offsets, hits, max_hits);
+      total = hits.size();
+      std::vector<std::pair<Locator::hit_type, size_type>> rows;
+      std::string lines;
+      for(size_type k = 0; k < patterns.size(); k++)
       {
-        lines += std::to_string(k); lines += '\t'; lines += std::to_string(hits[h].first); lines += '\t'; lines += std::to_string(hits[h].second); lines += '\n';
+        rows.clear();
+        for(size_type s = string_offsets[k]; s < string_offsets[k + 1]; s++)
+        {
+          for(size_type h = hit_offsets[s]; h < hit_offsets[s + 1]; h++) { rows.push_back(std::make_pair(hits[h], strings[s].mismatches)); }
+        }
+        if(rows.empty()) { continue; }
+        found++;
+        std::sort(rows.begin(), rows.end());
+        lines.clear();
+        for(const auto& row : rows)
+        {
+          lines += std::to_string(k); lines += '\t'; lines += std::to_string(row.first.first); lines += '\t'; lines += std::to_string(row.first.second); lines += '\t';
+          lines += std::to_string(row.second); lines += '\n';
+        }
+        out.write(lines.data(), (std::streamsize)lines.size());
       }
-      out.write(lines.data(), (std::streamsize)lines.size());
+    }
+    else
+    {
+      bwtm_index* ix = fmi.bwt.onDevice(fmi.alpha.C);
+      gpuCheck(bwtm_find_batch(ix, text.data(), offsets.data(), patterns.size(), sp.data(), ep.data()), "bwt_locate");
+      std::vector<range_type> ranges(patterns.size());
+      for(size_type k = 0; k < patterns.size(); k++) { ranges[k] = range_type(sp[k], ep[k]); }
+
+      Locator locator(fmi, max_len);
+      std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
+      locator.locate(ranges, hit_offsets, hits, max_hits);
+      total = hits.size();
+      std::string lines;
+      for(size_type k = 0; k < patterns.size(); k++)
+      {
+        if(hit_offsets[k + 1] == hit_offsets[k]) { continue; }
+        found++;
+        std::sort(hits.begin() + hit_offsets[k], hits.begin() + hit_offsets[k + 1]);
+        lines.clear();
+        for(size_type h = hit_offsets[k]; h < hit_offsets[k + 1]; h++)
+        {
+          lines += std::to_string(k); lines += '\t'; lines += std::to_string(hits[h].first); lines += '\t'; lines += std::to_string(hits[h].second); lines += '\n';
+        }
+        out.write(lines.data(), (std::streamsize)lines.size());
+      }
     }
   }
   out.close();

@@ -144,6 +144,34 @@ public:
   }
   template<class Container> range_type find(const Container& pattern) const { return find(pattern.begin(), pattern.end()); }
 
+  // One string within max_mismatches substitutions of a pattern that occurs in the collection: its range, as find() returns it, and the
+  // number of places in which it differs.
+  struct ApproxHit
+  {
+    range_type range; size_type mismatches;
+  };
+
+  // Backward search with up to max_mismatches (0..8) substitutions of patterns given as comp values 1..5: pattern k is
+  // text[offsets[k] .. offsets[k + 1]), its hits are hits[hit_offsets[k] .. hit_offsets[k + 1]), ascending when the matched strings are
+  // compared from their last symbol backwards; max_hits > 0 keeps the first max_hits of every pattern.  On the device
+  // (bwtm_find_approx_batch: a sizing call, then the filling one).  The index goes to the device if it is not there, and stays.
+  void findApprox(const std::vector<byte_type>& text, const std::vector<uint64_t>& offsets, size_type max_mismatches, std::vector<size_type>& hit_offsets,
+    std::vector<ApproxHit>& hits, size_type max_hits = 0) const
+  {
+    const size_type count = (offsets.empty() ? 0 : offsets.size() - 1);
+    hit_offsets.assign(count + 1, 0); hits.clear();
+    if(count == 0) { return; }
+    bwtm_index* ix = bwt.onDevice(alpha.C);
+    const uint32_t d = (uint32_t)std::min<size_type>(max_mismatches, ~(uint32_t)0);
+    gpuCheck(bwtm_find_approx_batch(ix, text.data(), offsets.data(), count, d, max_hits, hit_offsets.data(), nullptr, nullptr, nullptr, 0), "FMI::findApprox()");
+    const size_type total = hit_offsets[count];
+    if(total == 0) { return; }
+    std::vector<uint64_t> sp(total), len(total); std::vector<uint8_t> mm(total);
+    gpuCheck(bwtm_find_approx_batch(ix, text.data(), offsets.data(), count, d, max_hits, hit_offsets.data(), sp.data(), len.data(), mm.data(), total), "FMI::findApprox()");
+    hits.resize(total);
+    for(size_type h = 0; h < total; h++) { hits[h].range = range_type(sp[h], sp[h] + len[h] - 1); hits[h].mismatches = mm[h]; }
+  }
+
   // The sequences with the ids [ids.first, ids.second] as comp values 1..5 in forward order, endmarkers not included: sequence k of the
   // range is text[offsets[k] .. offsets[k + 1]).  LF walks on the device (bwtm_sequences_extract: a sizing call, then the extracting one);
   // no sequence may be longer than max_len (0: 65536).  The index goes to the device if it is not there, and stays.

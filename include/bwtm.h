@@ -156,6 +156,35 @@ int bwtm_inverse_select_batch(const bwtm_index* index, const uint64_t* positions
    (BWTM_EINVAL names the first pattern whose end lies before its begin); patterns holds offsets[count] bytes. */
 int bwtm_find_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
                     uint64_t* out_sp, uint64_t* out_ep);
+/* Backward search of `count` patterns with up to max_mismatches (0..8) substitutions: no indels, no reverse complements.  Patterns are
+   laid out as for bwtm_find_batch, comp values 1..5 (N's comp value is a symbol like the others); at most 65 535 symbols each.
+   A HIT of a pattern P of m symbols is a string W of m comp values 1..5 that occurs inside a sequence (nothing spans an endmarker)
+   and differs from P in at most max_mismatches places.  It is reported once, as (sp, count, mismatches): [sp, sp + count - 1] is
+   the closed range bwtm_find_batch returns for W, ready for bwtm_locate_ranges, and mismatches the number of places.  Distinct hits
+   have disjoint ranges.  The empty pattern has the single hit (0, bases, 0); with max_mismatches == 0 a pattern has one hit, the
+   range of bwtm_find_batch, or none when that range is empty.
+   ORDER: the hits of a pattern are ascending when the matched strings W are compared from their LAST symbol backwards (the order in
+   which a backward search that tries the comp values 1..5 in turn meets them; nothing is sorted).  max_hits > 0 keeps the first
+   max_hits hits of every pattern in that order.  The result is the same from run to run.
+   hit_offsets[count + 1] always receives the exclusive prefix sums of the kept hits.  capacity == 0, or all three output arrays NULL:
+   sizes only (the search still runs).  Otherwise capacity >= hit_offsets[count] (BWTM_EINVAL if not, and nothing is written) and the
+   hits of pattern k occupy [hit_offsets[k], hit_offsets[k + 1]) of out_sp / out_count / out_mismatches, any of which may be NULL;
+   nothing behind hit_offsets[count] is touched.
+   The Hamming neighbours of a pattern share every prefix of the search: the patterns of a batch are one frontier of ranges, expanded
+   level by level (two launches, one scan and one small read-back per level; as many levels as the longest pattern has symbols),
+   and a branch dies when its range is empty.  The call works in batches of bwtm_tune("approx_batch") patterns (default 2^16, at
+   most 2^28, 0 restores the default), because a frontier's size is known only once it has been counted.  Device memory beyond
+   the index, per batch, with P = its largest frontier (at least its patterns), H = its hits before max_hits and T = the bytes of its
+   pattern text: at most 240 P + 128 H + 2 T + 2^20 bytes while every block stays below 512 MiB (api/approx.hip.h derives it).
+   A frontier or hit buffer that does not fit the device is BWTM_ENOMEM: lower approx_batch or max_mismatches.
+   Works on any whole index, not on a window.  BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument, a window
+   of an index, max_mismatches > 8, offsets that decrease, a pattern longer than 65 535 symbols, a pattern symbol outside 1..5. */
+int bwtm_find_approx_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
+                           uint32_t max_mismatches, uint64_t max_hits, uint64_t* hit_offsets /* count + 1 */,
+                           uint64_t* out_sp, uint64_t* out_count, uint8_t* out_mismatches, uint64_t capacity);
+/* What the calling thread's last bwtm_find_approx_batch did: stats[0] = nodes expanded (the sizes of all frontiers, every batch
+   once), stats[1] = P and stats[2] = H of the formula above (the largest over the batches), stats[3] = levels run. */
+int bwtm_find_approx_stats(uint64_t stats[4]);
 /* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each.  first <= bases and
    count <= bases - first, or BWTM_EINVAL (a sum that wraps included); first == bases with count == 0 is accepted. */
 int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_t* out);
