@@ -155,6 +155,13 @@ SYMBOLS = [
     ("bwtm_kmers_levels", C.c_int, [vp, p_u64]),
     ("bwtm_kmers_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64]),
     ("bwtm_kmers_histogram", C.c_int, [vp, u64, p_u64]),
+    ("bwtm_kmer_join_create", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64, u64, u64, u64, u64, C.POINTER(vp)]),
+    ("bwtm_kmer_join_free", None, [vp]),
+    ("bwtm_kmer_join_distinct", u64, [vp]),
+    ("bwtm_kmer_join_bytes", u64, [vp]),
+    ("bwtm_kmer_join_levels", C.c_int, [vp, p_u64]),
+    ("bwtm_kmer_join_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64, p_u64, p_u64]),
+    ("bwtm_kmer_join_summary", C.c_int, [vp, p_u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -819,6 +826,11 @@ class Index:
         """The distinct k-mers of the collection with their counts and BWT ranges (bwtm_kmers_create); skip = the comp of N."""
         return Kmers(self, k, skip, min_count)
 
+    def kmer_join(self, other, k, skip=5, min_a=0, max_a=None, min_b=0, max_b=None, min_sum=1):
+        """The k-mers of this index (a) and of `other` (b) side by side, with their counts and insertion points in each
+        (bwtm_kmer_join_create); max_x=None: no upper bound."""
+        return KmerJoin(self, other, k, skip, min_a, max_a, min_b, max_b, min_sum)
+
 
 KMER_MAX_K = 32
 
@@ -887,6 +899,65 @@ class Kmers:
         hist = np.zeros(max(int(bins), 0), dtype=np.uint64)
         check(lib().bwtm_kmers_histogram(self.h, int(bins), hist.ctypes.data_as(p_u64)))
         return hist
+
+
+KMER_JOIN_NO_BOUND = (1 << 64) - 1
+KMER_JOIN_STATS = ("only_a", "only_b", "both", "only_a_occurrences_a", "only_b_occurrences_b", "both_occurrences_a", "both_occurrences_b")
+
+
+class KmerJoin:
+    """The kept k-mers of two indexes in ascending order with their counts and insertion points in each, on the device (handle on
+    bwtm_kmer_join).  It does not borrow the indexes."""
+
+    def __init__(self, a, b, k, skip=5, min_a=0, max_a=None, min_b=0, max_b=None, min_sum=1):
+        out = vp()
+        check(lib().bwtm_kmer_join_create(a.h, b.h, int(k), int(skip), int(min_a), KMER_JOIN_NO_BOUND if max_a is None else int(max_a),
+                                          int(min_b), KMER_JOIN_NO_BOUND if max_b is None else int(max_b), int(min_sum), C.byref(out)))
+        self.h = out
+        self.k, self.skip = int(k), int(skip)
+
+    distinct = property(lambda s: int(lib().bwtm_kmer_join_distinct(s.h)))
+    nbytes = property(lambda s: int(lib().bwtm_kmer_join_bytes(s.h)))
+
+    def free(self):
+        if self.h:
+            lib().bwtm_kmer_join_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h:
+            raise BwtmError("the k-mer join has been freed")
+
+    def levels(self):
+        """nodes[t] = the (t + 1)-mers the lower bounds keep for t < k - 1; nodes[k - 1] = the result (upper bounds applied)."""
+        self._live()
+        nodes = np.zeros(KMER_MAX_K, dtype=np.uint64)
+        check(lib().bwtm_kmer_join_levels(self.h, nodes.ctypes.data_as(p_u64)))
+        return nodes[: self.k]
+
+    def download(self, first=0, count=None):
+        """(codes, count_a, count_b, sp_a, sp_b) of the entries [first, first + count) (count=None: up to the last one)."""
+        self._live()
+        if count is None:
+            count = max(self.distinct - int(first), 0)
+        if int(first) + int(count) > self.distinct:                      # the library says so, before arrays of that size are made
+            check(lib().bwtm_kmer_join_download(self.h, int(first), int(count), None, None, None, None, None))
+        arrays = tuple(np.zeros(int(count), dtype=np.uint64) for _ in range(5))
+        check(lib().bwtm_kmer_join_download(self.h, int(first), int(count), *[a.ctypes.data_as(p_u64) for a in arrays]))
+        return arrays
+
+    def summary(self):
+        """The seven numbers of bwtm_kmer_join_summary by name (KMER_JOIN_STATS)."""
+        self._live()
+        stats = np.zeros(7, dtype=np.uint64)
+        check(lib().bwtm_kmer_join_summary(self.h, stats.ctypes.data_as(p_u64)))
+        return dict(zip(KMER_JOIN_STATS, (int(v) for v in stats)))
 
 
 class Locator:

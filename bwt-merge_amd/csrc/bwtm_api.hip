@@ -18,6 +18,7 @@
     api/locate.hip.h    positions to (sequence id, offset): the locator's table, positions and ranges located in batches
     api/overlap.hip.h   suffix-prefix overlaps: one backward search per query, counted, then emitted and expanded through the locator's table
     api/kmers.hip.h     the distinct k-mers of an index with counts and ranges: the trie's levels on two ping-pong frontiers, the spectrum
+    api/kmer_join.hip.h the k-mers of two indexes with their counts and insertion points in each: one joint walk, the summary of the result
     api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
@@ -61,4 +62,5 @@ using namespace bwtm;
 #include "api/locate.hip.h"
 #include "api/overlap.hip.h"
 #include "api/kmers.hip.h"
+#include "api/kmer_join.hip.h"
 #include "api/approx.hip.h"

@@ -46,6 +46,10 @@
                        the distinct k-mers with their counts: the suffix trie down to depth k, level by level, every level the stable
                        split by symbol of the one before (count pass, scan, expand-and-scatter pass), and the spectrum of the result
                        (kernels/kmers.hip.h; no counterpart in the reference)
+    k_kmer_join_level<EMIT>, k_kmer_join_summary
+                       the k-mers of two indexes side by side: one joint walk down both suffix tries, a node a range in each index
+                       (an insertion point where the string is absent), the same stable split per level, and the summary of the result
+                       (kernels/kmer_join.hip.h; the first levels of the merger's own search, generalised; no counterpart in the reference)
     k_approx_roots, k_approx_level<EMIT>, k_approx_mark, k_approx_cap, k_approx_gather
                        patterns with up to d substitutions: the backward search of a batch as one frontier of (range, pattern, symbols
                        left, mismatches spent), every level a count pass, a scan and an expand pass into the next frontier and the hit
@@ -102,6 +106,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/locate.hip.h"
 #include "kernels/overlap.hip.h"
 #include "kernels/kmers.hip.h"
+#include "kernels/kmer_join.hip.h"
 #include "kernels/approx.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"

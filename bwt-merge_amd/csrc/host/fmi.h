@@ -310,6 +310,68 @@ private:
   bwtm_kmers* handle = nullptr;
 };
 
+// The k-mers of two FMIs' collections side by side, ascending, on the device (bwtm_kmer_join_create): every kept k-mer with its count and
+// its insertion point in each.  A k-mer is kept when min_a <= count in a <= max_a, min_b <= count in b <= max_b and the two counts add up to
+// min_sum or more; NO_BOUND is no upper bound.  Both indexes go to the device if they are not there, and stay; the result borrows neither.
+// The two alphabets must be the same one: a code means the same string on both sides.
+class KmerJoin
+{
+public:
+  typedef BWT::size_type size_type;
+  constexpr static size_type NO_BOUND = ~(size_type)0;
+  constexpr static size_type STATS = 7;
+
+  KmerJoin(const FMI& a, const FMI& b, size_type k, size_type skip, size_type min_a = 0, size_type max_a = NO_BOUND, size_type min_b = 0, size_type max_b = NO_BOUND,
+    size_type min_sum = 1) : k(k), skip(skip)
+  {
+    if(a.alpha != b.alpha)
+    {
+      std::cerr << "KmerJoin::KmerJoin(): Cannot compare BWTs with different alphabets" << std::endl;
+      std::exit(EXIT_FAILURE);
+    }
+    const bwtm_index* da = a.bwt.onDevice(a.alpha.C);
+    const bwtm_index* db = (&a == &b ? da : b.bwt.onDevice(b.alpha.C));
+    gpuCheck(bwtm_kmer_join_create(da, db, (uint32_t)std::min<size_type>(k, ~(uint32_t)0), (uint32_t)std::min<size_type>(skip, ~(uint32_t)0), min_a, max_a, min_b, max_b, min_sum,
+      &this->handle), "KmerJoin::KmerJoin()");
+  }
+  ~KmerJoin() { bwtm_kmer_join_free(this->handle); }
+  KmerJoin(const KmerJoin&) = delete; KmerJoin& operator=(const KmerJoin&) = delete;
+
+  size_type distinct() const { return bwtm_kmer_join_distinct(this->handle); }
+  size_type bytes() const { return bwtm_kmer_join_bytes(this->handle); }
+
+  // The entries [first, first + count) in ascending order; the insertion points may be null.
+  void download(size_type first, size_type count, std::vector<uint64_t>& codes, std::vector<uint64_t>& count_a, std::vector<uint64_t>& count_b,
+    std::vector<uint64_t>* sp_a = nullptr, std::vector<uint64_t>* sp_b = nullptr) const
+  {
+    codes.resize(count); count_a.resize(count); count_b.resize(count);
+    if(sp_a) { sp_a->resize(count); }
+    if(sp_b) { sp_b->resize(count); }
+    gpuCheck(bwtm_kmer_join_download(this->handle, first, count, codes.data(), count_a.data(), count_b.data(), (sp_a ? sp_a->data() : nullptr), (sp_b ? sp_b->data() : nullptr)),
+      "KmerJoin::download()");
+  }
+
+  // k-mers only in a, only in b, in both; occurrences in a of the first, in b of the second, in a and in b of the third.
+  std::vector<uint64_t> summary() const
+  {
+    std::vector<uint64_t> stats(STATS, 0);
+    gpuCheck(bwtm_kmer_join_summary(this->handle, stats.data()), "KmerJoin::summary()");
+    return stats;
+  }
+
+  // Symbol j (0 = first) of a code as its comp value.
+  byte_type comp(uint64_t code, size_type j) const
+  {
+    const size_type rank = (code >> (2 * (k - 1 - j))) & 3;
+    return (byte_type)(rank + 1 + (rank + 1 >= skip ? 1 : 0));
+  }
+
+  const size_type k, skip;
+
+private:
+  bwtm_kmer_join* handle = nullptr;
+};
+
 // Search phase (buildRA, reference fmi.cpp:272-334) as a free function: makes sure a and b are on the device and
 // fills a device rank array; parameters.sequence_blocks splits the sequences of b.
 inline void buildRA(const FMI& a, const FMI& b, const MergeParameters& parameters, RankArray& ra)

@@ -284,6 +284,44 @@ int bwtm_kmers_download(const bwtm_kmers* kmers, uint64_t first, uint64_t count,
 /* hist[j] = number of kept k-mers of count j for j < bins - 1; hist[bins - 1] = those of count >= bins - 1; bins >= 2 */
 int bwtm_kmers_histogram(const bwtm_kmers* kmers, uint64_t bins, uint64_t* hist);
 
+/* The k-mers of TWO collections side by side: which k-mers a and b share and which only one of them holds (sample against sample,
+   reads against a reference, a new batch against the index it is about to be merged into).  k, skip, codes and counts are those
+   of bwtm_kmers_create.  Both suffix tries are walked down together, so every entry carries, for each index x, its count cnt_x
+   and sp_x: the first position of its BWT range in x when cnt_x > 0 (the range bwtm_find_batch returns), and otherwise its
+   INSERTION POINT, the number of suffixes of x that are smaller than the k-mer.  For the merged index of a and b the k-mer's
+   count is cnt_a + cnt_b and its sp is sp_a + sp_b.
+   A k-mer is kept when  min_a <= cnt_a <= max_a,  min_b <= cnt_b <= max_b  and  cnt_a + cnt_b >= min_sum.  min_a and min_b may
+   be 0 (the k-mer may be absent there); a min_sum of 0 is taken as 1 (a k-mer neither index holds is never listed); max_x ==
+   UINT64_MAX is no bound.  All defaults (0, UINT64_MAX, 0, UINT64_MAX, 1): the union with both counts.  min_a = min_b = 1: the
+   shared k-mers.  min_b = m, max_a = 0: in b at least m times and absent from a.  The lower bounds prune every level of the walk,
+   the upper bounds act at level k only.
+   The result lists the kept k-mers in ascending code order, which is ascending sp_a and ascending sp_b as well (both non-strict),
+   and lives on the device; it does not borrow the indexes once created.  a and b may be the same handle: then both sides are equal.
+   The walk is 2 (k - 1) launches over frontiers of 40 bytes per node and one small read-back per level.  Works on any two whole
+   indexes of one context (uploaded, merged, built; records and super table suffice), not on a window.
+   Device memory of the call beyond the two indexes, with P = the largest entry of bwtm_kmer_join_levels: at most 392 P + 2^20
+   bytes while every block stays below 512 MiB (api/kmer_join.hip.h derives it); the handle keeps 40 bytes per kept k-mer and
+   nothing else.  A result that does not fit the device is BWTM_ENOMEM: raise a lower bound or lower k.
+   BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument, a window of an index on either side, indexes of
+   different contexts, k == 0 or k > 32, skip outside 1..5, min_a > max_a, min_b > max_b, first + count beyond
+   bwtm_kmer_join_distinct (a sum that wraps included). */
+typedef struct bwtm_kmer_join bwtm_kmer_join;
+int bwtm_kmer_join_create(const bwtm_index* a, const bwtm_index* b, uint32_t k, uint32_t skip,
+                          uint64_t min_a, uint64_t max_a, uint64_t min_b, uint64_t max_b, uint64_t min_sum,
+                          bwtm_kmer_join** out);
+void bwtm_kmer_join_free(bwtm_kmer_join* join);
+uint64_t bwtm_kmer_join_distinct(const bwtm_kmer_join* join);      /* kept k-mers */
+uint64_t bwtm_kmer_join_bytes(const bwtm_kmer_join* join);         /* device bytes the handle holds */
+/* nodes[t] for t < k - 1 = the (t + 1)-mers the lower bounds keep: the frontier after each level; nodes[k - 1] = the result, after
+   the upper bounds as well; 0 behind k */
+int bwtm_kmer_join_levels(const bwtm_kmer_join* join, uint64_t nodes[32]);
+/* entries [first, first + count) in code order; any of the five output arrays may be NULL */
+int bwtm_kmer_join_download(const bwtm_kmer_join* join, uint64_t first, uint64_t count,
+                            uint64_t* codes, uint64_t* count_a, uint64_t* count_b, uint64_t* sp_a, uint64_t* sp_b);
+/* Over the kept k-mers: stats[0], [1], [2] = those only in a (cnt_b == 0), only in b (cnt_a == 0), in both; stats[3] = the
+   occurrences in a of the first class, stats[4] = those in b of the second, stats[5], stats[6] = those in a and in b of the third */
+int bwtm_kmer_join_summary(const bwtm_kmer_join* join, uint64_t stats[7]);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
