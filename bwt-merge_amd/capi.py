@@ -13,6 +13,7 @@ SIGMA = 6
 
 u64 = C.c_uint64
 p_u8 = C.POINTER(C.c_uint8)
+p_u32 = C.POINTER(C.c_uint32)
 p_u64 = C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
@@ -138,6 +139,8 @@ SYMBOLS = [
     ("bwtm_find_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u64, p_u64]),
     ("bwtm_find_approx_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, u64, p_u64, p_u64, p_u64, p_u8, u64]),
     ("bwtm_find_approx_stats", C.c_int, [p_u64]),
+    ("bwtm_find_edit_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, u64, p_u64, p_u64, p_u64, p_u8, p_u32, u64]),
+    ("bwtm_find_edit_stats", C.c_int, [p_u64]),
     ("bwtm_extract", C.c_int, [vp, u64, u64, p_u8]),
     ("bwtm_sequences_extract", C.c_int, [vp, p_u64, u64, u64, u64, p_u64, p_u8, u64]),
     ("bwtm_locator_create", C.c_int, [vp, u64, C.POINTER(vp)]),
@@ -796,6 +799,30 @@ class Index:
                                                mismatches.ctypes.data_as(p_u8), total))
         return hit_offsets, sp, count, mismatches
 
+    def find_edit(self, patterns, max_edits, max_hits=0):
+        """Backward search within edit distance max_edits, indels included (bwtm_find_edit_batch).  Returns (hit_offsets [count + 1], sp,
+        count, edits, lengths): the hits of pattern k are [hit_offsets[k], hit_offsets[k + 1]), each the range [sp, sp + count - 1] of one
+        matched string of `lengths` symbols at distance `edits`, shortest first and, within a length, ascending when the strings are
+        compared from their last symbol backwards.  One sizing call, then the filling call."""
+        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lens)
+        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+        text, tp = _u8(text)
+        hit_offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        check(lib().bwtm_find_edit_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_edits), int(max_hits),
+                                         hit_offsets.ctypes.data_as(p_u64), None, None, None, None, 0))
+        total = int(hit_offsets[-1])
+        sp = np.zeros(total, dtype=np.uint64)
+        count = np.zeros(total, dtype=np.uint64)
+        edits = np.zeros(total, dtype=np.uint8)
+        lengths = np.zeros(total, dtype=np.uint32)
+        if total > 0:
+            check(lib().bwtm_find_edit_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_edits), int(max_hits),
+                                             hit_offsets.ctypes.data_as(p_u64), sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64),
+                                             edits.ctypes.data_as(p_u8), lengths.ctypes.data_as(p_u32), total))
+        return hit_offsets, sp, count, edits, lengths
+
     def extract(self, first, count):
         out = np.zeros(count, dtype=np.uint8)
         check(lib().bwtm_extract(self.h, first, count, out.ctypes.data_as(p_u8)))
@@ -1026,6 +1053,15 @@ class Locator:
         hit_offsets, sp, count, mismatches = self.index.find_approx(patterns, max_mismatches, max_hits)
         occ_offsets, ids, offs = self.locate_ranges(sp, sp + count - np.uint64(1))
         return hit_offsets, sp, count, mismatches, occ_offsets, ids, offs
+
+    def locate_edit(self, patterns, max_edits, max_hits=0):
+        """Every occurrence of every pattern within edit distance max_edits: Index.find_edit, then locate_ranges on the hits' ranges.
+        Returns (hit_offsets, sp, count, edits, lengths) of find_edit (max_hits caps the hits of a pattern, not their occurrences) and
+        (occ_offsets, ids, offsets) of locate_ranges over the hits: hit h occurs at offsets[j] of sequence ids[j] for j in
+        [occ_offsets[h], occ_offsets[h + 1]), over lengths[h] symbols."""
+        hit_offsets, sp, count, edits, lengths = self.index.find_edit(patterns, max_edits, max_hits)
+        occ_offsets, ids, offs = self.locate_ranges(sp, sp + count - np.uint64(1))
+        return hit_offsets, sp, count, edits, lengths, occ_offsets, ids, offs
 
     def _overlap_calls(self, call, count, max_hits):
         """The sizing call, then the real one: call(hit_offsets, ids, lengths, capacity) is one of the two C calls with its queries bound."""
@@ -1478,6 +1514,14 @@ def find_approx_stats():
     nodes expanded, the largest frontier of a batch, the most hits of a batch before max_hits, levels run."""
     stats = np.zeros(4, dtype=np.uint64)
     check(lib().bwtm_find_approx_stats(stats.ctypes.data_as(p_u64)))
+    return dict(expanded=int(stats[0]), frontier_peak=int(stats[1]), batch_hits=int(stats[2]), levels=int(stats[3]))
+
+
+def find_edit_stats():
+    """What the calling thread's last Index.find_edit call did (bwtm_find_edit_stats; of its second, filling call when there were hits):
+    nodes expanded, the largest frontier of a batch, the most hits of a batch before max_hits, levels run."""
+    stats = np.zeros(4, dtype=np.uint64)
+    check(lib().bwtm_find_edit_stats(stats.ctypes.data_as(p_u64)))
     return dict(expanded=int(stats[0]), frontier_peak=int(stats[1]), batch_hits=int(stats[2]), levels=int(stats[3]))
 
 

@@ -20,6 +20,7 @@
     api/kmers.hip.h     the distinct k-mers of an index with counts and ranges: the trie's levels on two ping-pong frontiers, the spectrum
     api/kmer_join.hip.h the k-mers of two indexes with their counts and insertion points in each: one joint walk, the summary of the result
     api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern
+    api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -64,3 +65,4 @@ using namespace bwtm;
 #include "api/kmers.hip.h"
 #include "api/kmer_join.hip.h"
 #include "api/approx.hip.h"
+#include "api/edit.hip.h"

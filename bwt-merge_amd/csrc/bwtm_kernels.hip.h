@@ -55,6 +55,11 @@
                        left, mismatches spent), every level a count pass, a scan and an expand pass into the next frontier and the hit
                        stream, both in parent-then-symbol order; then every pattern's hits found by their neighbours and gathered
                        (kernels/approx.hip.h; no counterpart in the reference)
+    k_edit_roots, k_edit_level<EMIT>, k_edit_mark, k_edit_cap, k_edit_gather
+                       patterns within edit distance e: the same frontier, a node (range, pattern, 15 fields of the edit-distance
+                       column around its depth), a child kept for the next frontier and / or a hit, independently, so that a pattern's
+                       hits appear over 2 e + 1 levels; then marked and gathered per pattern and length
+                       (kernels/edit.hip.h; no counterpart in the reference)
 */
 #pragma once
 
@@ -108,6 +113,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/kmers.hip.h"
 #include "kernels/kmer_join.hip.h"
 #include "kernels/approx.hip.h"
+#include "kernels/edit.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

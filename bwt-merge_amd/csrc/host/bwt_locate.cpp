@@ -5,9 +5,10 @@
   line, and mapped exactly as `bwt_merge -v` reads them.  The output holds one line per hit,
       pattern_number <TAB> sequence <TAB> offset        (all 0-based)
   in the order of the patterns and, within a pattern, sorted by (sequence, offset): two runs compare with cmp.
-  With -d N the search allows up to N substitutions (bwtm_find_approx_batch: no indels, no reverse complements) and every line gains a
+  With -d N the search allows up to N substitutions (bwtm_find_approx_batch: no reverse complements) and every line gains a
   fourth column, the number of places in which the occurrence differs from the pattern; -x then bounds the occurrences written per
-  matched string.  Without -d the output is what it always was.
+  matched string.  With -e N it allows up to N insertions, deletions and substitutions (bwtm_find_edit_batch) and every line gains
+  two columns, the edit distance of the occurrence from the pattern and its length.  Without -d and -e the output is what it always was.
   Sequence k of an index built by bwt_ingest, or merged from such indexes by bwt_merge, is read k of the input(s) in order.
 */
 #include <unistd.h>
@@ -27,7 +28,9 @@ static void printUsage()
   std::cerr << "  -m N           Longest sequence the input may hold (default: 65536, at most 16777216)" << std::endl;
   std::cerr << "  -x N           Write at most N hits per pattern: the first N positions of its range (default: all)" << std::endl;
   std::cerr << "  -d N           Allow up to N substitutions, 0 to 8, and write the mismatches of every hit as a fourth column;" << std::endl;
-  std::cerr << "                 -x then applies to every matched string (default: exact search, three columns)" << std::endl << std::endl;
+  std::cerr << "                 -x then applies to every matched string (default: exact search, three columns)" << std::endl;
+  std::cerr << "  -e N           Allow up to N edits (insertions, deletions, substitutions), 0 to 7, and write the edit distance and the" << std::endl;
+  std::cerr << "                 length of every hit as a fourth and fifth column; -x as with -d; not together with -d" << std::endl << std::endl;
   printFormats(std::cerr);
 }
 
@@ -49,9 +52,9 @@ int main(int argc, char** argv)
 
   int device = 0;
   std::string input_tag = NativeFormat::tag();
-  size_type max_len = 0, max_hits = 0, mismatches = 0;
-  bool approx = false;
-  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:d:")) != -1; )
+  size_type max_len = 0, max_hits = 0, mismatches = 0, edits = 0;
+  bool approx = false, edit = false;
+  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:d:e:")) != -1; )
   {
     switch(c)
     {
@@ -66,15 +69,21 @@ int main(int argc, char** argv)
       approx = true; mismatches = std::stoull(optarg);
       if(mismatches > 8) { std::cerr << "bwt_locate: -d takes 0 to 8 mismatches" << std::endl; std::exit(EXIT_FAILURE); }
       break;
+    case 'e':
+      edit = true; edits = std::stoull(optarg);
+      if(edits > 7) { std::cerr << "bwt_locate: -e takes 0 to 7 edits" << std::endl; std::exit(EXIT_FAILURE); }
+      break;
     default: std::exit(EXIT_FAILURE);
     }
   }
+  if(approx && edit) { std::cerr << "bwt_locate: -d and -e cannot be used together" << std::endl; std::exit(EXIT_FAILURE); }
   if(optind + 2 >= argc) { std::cerr << "bwt_locate: Input, pattern and output files must be specified" << std::endl; std::exit(EXIT_FAILURE); }
   std::string input_name = argv[optind], pattern_name = argv[optind + 1], output_name = argv[optind + 2];
   std::cout << "Input:    " << input_name << " (" << input_tag << ")" << std::endl;
   std::cout << "Patterns: " << pattern_name << std::endl;
-  std::cout << "Output:   " << output_name << (approx ? " (pattern, sequence, offset, mismatches)" : " (pattern, sequence, offset)") << std::endl;
+  std::cout << "Output:   " << output_name << (edit ? " (pattern, sequence, offset, edits, length)" : approx ? " (pattern, sequence, offset, mismatches)" : " (pattern, sequence, offset)") << std::endl;
   if(approx) { std::cout << "Search:   up to " << mismatches << " substitutions" << std::endl; }
+  if(edit) { std::cout << "Search:   up to " << edits << " edits" << std::endl; }
   std::cout << std::endl;
 
   double start = readTimer();
@@ -125,6 +134,38 @@ int main(int argc, char** argv)
         {
           lines += std::to_string(k); lines += '\t'; lines += std::to_string(row.first.first); lines += '\t'; lines += std::to_string(row.first.second); lines += '\t';
           lines += std::to_string(row.second); lines += '\n';
+        }
+        out.write(lines.data(), (std::streamsize)lines.size());
+      }
+    }
+    else if(edit)
+    {
+      // as with -d: every matched string is a range of its own, its distance and length written with every occurrence
+      std::vector<size_type> string_offsets; std::vector<FMI::EditHit> strings;
+      fmi.findEdit(text, offsets, edits, string_offsets, strings);
+      std::vector<range_type> ranges(strings.size());
+      for(size_type s = 0; s < strings.size(); s++) { ranges[s] = strings[s].range; }
+      Locator locator(fmi, max_len);
+      std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
+      locator.locate(ranges, hit_offsets, hits, max_hits);
+      total = hits.size();
+      std::vector<std::pair<Locator::hit_type, std::pair<size_type, size_type>>> rows;
+      std::string lines;
+      for(size_type k = 0; k < patterns.size(); k++)
+      {
+        rows.clear();
+        for(size_type s = string_offsets[k]; s < string_offsets[k + 1]; s++)
+        {
+          for(size_type h = hit_offsets[s]; h < hit_offsets[s + 1]; h++) { rows.push_back(std::make_pair(hits[h], std::make_pair(strings[s].edits, strings[s].length))); }
+        }
+        if(rows.empty()) { continue; }
+        found++;
+        std::sort(rows.begin(), rows.end());
+        lines.clear();
+        for(const auto& row : rows)
+        {
+          lines += std::to_string(k); lines += '\t'; lines += std::to_string(row.first.first); lines += '\t'; lines += std::to_string(row.first.second); lines += '\t';
+          lines += std::to_string(row.second.first); lines += '\t'; lines += std::to_string(row.second.second); lines += '\n';
         }
         out.write(lines.data(), (std::streamsize)lines.size());
       }

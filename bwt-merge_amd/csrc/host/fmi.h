@@ -172,6 +172,35 @@ public:
     for(size_type h = 0; h < total; h++) { hits[h].range = range_type(sp[h], sp[h] + len[h] - 1); hits[h].mismatches = mm[h]; }
   }
 
+  // One string within max_edits insertions, deletions and substitutions of a pattern that occurs in the collection: its range, as find()
+  // returns it, its Levenshtein distance from the pattern, and its length.
+  struct EditHit
+  {
+    range_type range; size_type edits; size_type length;
+  };
+
+  // Backward search within edit distance max_edits (0..7) of patterns given as comp values 1..5: pattern k is
+  // text[offsets[k] .. offsets[k + 1]), its hits are hits[hit_offsets[k] .. hit_offsets[k + 1]), shortest first and, within a length,
+  // ascending when the matched strings are compared from their last symbol backwards; max_hits > 0 keeps the first max_hits of every
+  // pattern.  On the device (bwtm_find_edit_batch: a sizing call, then the filling one).  The index goes to the device if it is not
+  // there, and stays.
+  void findEdit(const std::vector<byte_type>& text, const std::vector<uint64_t>& offsets, size_type max_edits, std::vector<size_type>& hit_offsets,
+    std::vector<EditHit>& hits, size_type max_hits = 0) const
+  {
+    const size_type count = (offsets.empty() ? 0 : offsets.size() - 1);
+    hit_offsets.assign(count + 1, 0); hits.clear();
+    if(count == 0) { return; }
+    bwtm_index* ix = bwt.onDevice(alpha.C);
+    const uint32_t e = (uint32_t)std::min<size_type>(max_edits, ~(uint32_t)0);
+    gpuCheck(bwtm_find_edit_batch(ix, text.data(), offsets.data(), count, e, max_hits, hit_offsets.data(), nullptr, nullptr, nullptr, nullptr, 0), "FMI::findEdit()");
+    const size_type total = hit_offsets[count];
+    if(total == 0) { return; }
+    std::vector<uint64_t> sp(total), len(total); std::vector<uint8_t> ed(total); std::vector<uint32_t> lengths(total);
+    gpuCheck(bwtm_find_edit_batch(ix, text.data(), offsets.data(), count, e, max_hits, hit_offsets.data(), sp.data(), len.data(), ed.data(), lengths.data(), total), "FMI::findEdit()");
+    hits.resize(total);
+    for(size_type h = 0; h < total; h++) { hits[h].range = range_type(sp[h], sp[h] + len[h] - 1); hits[h].edits = ed[h]; hits[h].length = lengths[h]; }
+  }
+
   // The sequences with the ids [ids.first, ids.second] as comp values 1..5 in forward order, endmarkers not included: sequence k of the
   // range is text[offsets[k] .. offsets[k + 1]).  LF walks on the device (bwtm_sequences_extract: a sizing call, then the extracting one);
   // no sequence may be longer than max_len (0: 65536).  The index goes to the device if it is not there, and stays.

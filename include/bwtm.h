@@ -156,7 +156,7 @@ int bwtm_inverse_select_batch(const bwtm_index* index, const uint64_t* positions
    (BWTM_EINVAL names the first pattern whose end lies before its begin); patterns holds offsets[count] bytes. */
 int bwtm_find_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
                     uint64_t* out_sp, uint64_t* out_ep);
-/* Backward search of `count` patterns with up to max_mismatches (0..8) substitutions: no indels, no reverse complements.  Patterns are
+/* Backward search of `count` patterns with up to max_mismatches (0..8) substitutions (bwtm_find_edit_batch allows insertions and deletions as well); no reverse complements.  Patterns are
    laid out as for bwtm_find_batch, comp values 1..5 (N's comp value is a symbol like the others); at most 65 535 symbols each.
    A HIT of a pattern P of m symbols is a string W of m comp values 1..5 that occurs inside a sequence (nothing spans an endmarker)
    and differs from P in at most max_mismatches places.  It is reported once, as (sp, count, mismatches): [sp, sp + count - 1] is
@@ -185,6 +185,40 @@ int bwtm_find_approx_batch(const bwtm_index* index, const uint8_t* patterns, con
 /* What the calling thread's last bwtm_find_approx_batch did: stats[0] = nodes expanded (the sizes of all frontiers, every batch
    once), stats[1] = P and stats[2] = H of the formula above (the largest over the batches), stats[3] = levels run. */
 int bwtm_find_approx_stats(uint64_t stats[4]);
+/* Backward search of `count` patterns within edit distance max_edits (0..7): insertions, deletions and substitutions at a cost of 1
+   each; no reverse complements.  Patterns are laid out as for bwtm_find_approx_batch, comp values 1..5 (N's comp value is a symbol
+   like the others); at most 65 535 symbols each.
+   A HIT of a pattern P of m symbols is a string W of comp values 1..5 that occurs inside a sequence (nothing spans an endmarker)
+   and whose Levenshtein distance ed(W, P) is <= max_edits; the alignment is global on both sides, the whole of W against the whole
+   of P.  It is reported once, as (sp, count, edits, length): [sp, sp + count - 1] is the closed range bwtm_find_batch returns for W,
+   ready for bwtm_locate_ranges, edits is ed(W, P) itself (the minimum, not the cost of the path that found W) and length is |W|,
+   m - max_edits <= |W| <= m + max_edits.  The ranges of distinct hits are disjoint or nested: W and Wx may both be hits.  When
+   m <= max_edits the empty string is a hit, (0, bases, m, 0).  With max_edits == 0 a pattern has one hit, the range of
+   bwtm_find_batch with edits = 0 and length = m, or none when that range is empty.
+   ORDER: the hits of a pattern come shortest W first and, within one length, ascending when the strings W are compared from their
+   LAST symbol backwards (the order of bwtm_find_approx_batch, per length; nothing is sorted).  max_hits > 0 keeps the first max_hits
+   hits of every pattern in that order.  The result is the same from run to run.
+   hit_offsets[count + 1] always receives the exclusive prefix sums of the kept hits.  capacity == 0, or all four output arrays NULL:
+   sizes only (the search still runs).  Otherwise capacity >= hit_offsets[count] (BWTM_EINVAL if not, and nothing is written) and the
+   hits of pattern k occupy [hit_offsets[k], hit_offsets[k + 1]) of out_sp / out_count / out_edits / out_lengths, any of which may be
+   NULL; nothing behind hit_offsets[count] is touched.
+   The strings near a pattern share every suffix of the search: W is built backwards, and its node carries the column
+   ed(W, last i symbols of P) for |i - |W|| <= 7.  A child is kept while its range is not empty and the least entry of its column
+   is within the budget, and is a hit when the entry of i = m is; the patterns of a batch are one frontier, expanded level by level
+   (two launches, one scan and one small read-back per level; at most longest pattern + max_edits levels).  The call works in batches of
+   bwtm_tune("approx_batch") patterns, as bwtm_find_approx_batch does, and a call of several batches searches each of them twice.
+   Device memory beyond the index, per batch, with P = its largest frontier (at least its patterns), H = its hits before max_hits,
+   T = the bytes of its pattern text and e = max_edits: at most (308 + 34 e) P + 132 H + 2 T + 2^20 bytes while every block stays
+   below 512 MiB (api/edit.hip.h derives it).  A frontier or hit buffer that does not fit the device is BWTM_ENOMEM: lower
+   approx_batch or max_edits.
+   Works on any whole index, not on a window.  BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument, a window
+   of an index, max_edits > 7, offsets that decrease, a pattern longer than 65 535 symbols, a pattern symbol outside 1..5. */
+int bwtm_find_edit_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
+                         uint32_t max_edits, uint64_t max_hits, uint64_t* hit_offsets /* count + 1 */,
+                         uint64_t* out_sp, uint64_t* out_count, uint8_t* out_edits, uint32_t* out_lengths, uint64_t capacity);
+/* What the calling thread's last bwtm_find_edit_batch did: stats[0] = nodes expanded (the sizes of all frontiers, every batch
+   once), stats[1] = P and stats[2] = H of the formula above (the largest over the batches), stats[3] = levels run. */
+int bwtm_find_edit_stats(uint64_t stats[4]);
 /* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each.  first <= bases and
    count <= bases - first, or BWTM_EINVAL (a sum that wraps included); first == bases with count == 0 is accepted. */
 int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_t* out);
