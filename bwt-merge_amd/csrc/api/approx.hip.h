@@ -8,7 +8,7 @@
 
       peak <= 240 P + 128 H + 2 T + 2^20 bytes                         (every block below 512 MiB)
 
-  192 P  two frontiers of 24 bytes per node, whose capacities at least double when they grow (api/kmers.hip.h: the blocks one frontier
+  192 P  two frontiers of 24 bytes per node, whose capacities at least double when they grow (api/frontier.hip.h: the blocks one frontier
          ever had hold fewer than 4 P nodes together, and a block taken back stays with the pool).
    96 H  the hit stream of the batch, 24 bytes per hit.  It grows by a level's hits at a time and keeps what it holds: the same doubling,
          so its blocks, the one being copied from included, hold fewer than 4 H hits together.
@@ -23,66 +23,40 @@
 
 namespace
 {
-u64 approx_batch_size() { return std::min<u64>((u64)g_tune.approx_batch, WALK_BATCH_LIMIT); }
-
 // What the last call of this thread did: nodes expanded (the frontiers' sizes summed over the levels and batches), the largest frontier
 // of a batch, the most hits of a batch before max_hits, levels run.
 thread_local u64 t_approx_stats[4] = {0, 0, 0, 0};
 
-ApproxNodes approx_nodes(const KmerFrontier& f, u64 capacity) { return ApproxNodes{f.sp(), f.cnt(), f.code(), std::min(capacity, f.cap)}; }
-
-// Room for `need` hits in the stream, of which the first `used` are kept.
-int approx_keep(KmerFrontier& hits, u64 used, u64 need)
-{
-  if(need <= hits.cap && hits.buf.p) { return BWTM_OK; }
-  KmerFrontier grown;
-  grown.cap = hits.cap;                                                                         // reserve() at least doubles this
-  TRY(grown.reserve(need));
-  if(used > 0)
-  {
-    HIP_TRY(hipMemcpyAsync(grown.sp(), hits.sp(), used * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(grown.cnt(), hits.cnt(), used * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(grown.code(), hits.code(), used * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-  }
-  hits.buf.swap(grown.buf); std::swap(hits.cap, grown.cap);
-  return BWTM_OK;                                                                               // the old block returns to the pool (stream ordered)
-}
+ApproxNodes approx_nodes(const Frontier<3>& f, u64 capacity) { return ApproxNodes{f.array(0), f.array(1), f.array(2), std::min(capacity, f.cap)}; }
 
 // One batch of patterns: the search, which leaves the hit stream, every pattern's slots in it and the batch's hit offsets on the device,
 // and the gather that brings the kept hits to the caller.
-struct ApproxBatch
+struct ApproxBatch : PatternBatch
 {
-  const bwtm_index* x = nullptr;
-  u32 max_mismatches = 0; u64 max_hits = 0;
-  DevBuf d_text, d_off, d_slots, d_base, d_totals, d_out;
-  u64 totals_cap = 0;
-  KmerFrontier cur, next, hits;
-  u64 nhits = 0, kept_total = 0;
-  std::vector<u64> h_off;
+  Frontier<3> cur, next;                               // sp, count, meta
 
   // One pass of a level over the frontier `cur`: the count pass, or the expand pass into `next` and the hit stream.
   template<bool QUAD>
-  int level(bool emit, const IndexView& v, u64 bytes, u64 nb, u64 count, u64 nblocks, u64 kept, u64 found)
+  int level(bool emit, const IndexView& v, u64 nb, u64 count, u64 nblocks, u64 kept, u64 found)
   {
-    u64* totals = d_totals.as<u64>();
     if(emit)
     {
-      LAUNCH("approx_expand", (k_approx_level<QUAD, true>), nblocks, BLOCK_THREADS, v, d_text.as<const u8>(), bytes, d_off.as<const u64>(), nb, max_mismatches,
-        (const u64*)cur.sp(), (const u64*)cur.cnt(), (const u64*)cur.code(), count, nblocks, totals, approx_nodes(next, kept), approx_nodes(hits, nhits + found), nhits);
+      LAUNCH("approx_expand", (k_approx_level<QUAD, true>), nblocks, BLOCK_THREADS, v, d_text.as<const u8>(), bytes, d_off.as<const u64>(), nb, max_cost,
+        (const u64*)cur.array(0), (const u64*)cur.array(1), (const u64*)cur.array(2), count, nblocks, totals.p(), approx_nodes(next, kept), hit_nodes(nhits + found), nhits);
     }
     else
     {
-      LAUNCH("approx_count", (k_approx_level<QUAD, false>), nblocks, BLOCK_THREADS, v, d_text.as<const u8>(), bytes, d_off.as<const u64>(), nb, max_mismatches,
-        (const u64*)cur.sp(), (const u64*)cur.cnt(), (const u64*)cur.code(), count, nblocks, totals, ApproxNodes{nullptr, nullptr, nullptr, 0}, ApproxNodes{nullptr, nullptr, nullptr, 0}, (u64)0);
+      LAUNCH("approx_count", (k_approx_level<QUAD, false>), nblocks, BLOCK_THREADS, v, d_text.as<const u8>(), bytes, d_off.as<const u64>(), nb, max_cost,
+        (const u64*)cur.array(0), (const u64*)cur.array(1), (const u64*)cur.array(2), count, nblocks, totals.p(), ApproxNodes{nullptr, nullptr, nullptr, 0}, ApproxNodes{nullptr, nullptr, nullptr, 0}, (u64)0);
     }
     return BWTM_OK;
   }
-  int level(bool emit, const IndexView& v, u64 bytes, u64 nb, u64 count, u64 nblocks, u64 kept, u64 found)
+  int level(bool emit, const IndexView& v, u64 nb, u64 count, u64 nblocks, u64 kept, u64 found)
   {
 #ifdef BWTM_DIAGNOSTICS
-    if(g_tune.approx_kernel == 1) { return level<true>(emit, v, bytes, nb, count, nblocks, kept, found); }      // the A/B partner: four lanes per node
+    if(g_tune.approx_kernel == 1) { return level<true>(emit, v, nb, count, nblocks, kept, found); }      // the A/B partner: four lanes per node
 #endif
-    return level<false>(emit, v, bytes, nb, count, nblocks, kept, found);
+    return level<false>(emit, v, nb, count, nblocks, kept, found);
   }
 
   u64* first() const { return d_slots.as<u64>(); }
@@ -91,39 +65,25 @@ struct ApproxBatch
   // The patterns first .. first + nb - 1 of the call; hit_offsets[0 .. nb] continue hit_offsets[0] by the kept counts.
   int search(const u8* patterns, const u64* offsets, u64 nb, u64* hit_offsets)
   {
+    const char* const who = "bwtm_find_approx_batch";
     const u64 before = hit_offsets[0];
-    const u64 base = offsets[0], bytes = offsets[nb] - base;
     const IndexView v = x->view();
 #ifdef BWTM_DIAGNOSTICS
     const u64 block_nodes = (g_tune.approx_kernel == 1 ? approx_block_nodes<true>() : approx_block_nodes<false>());
 #else
     const u64 block_nodes = approx_block_nodes<false>();
 #endif
-    h_off.resize(nb + 1);
-    u64 longest = 0;
-    for(u64 k = 0; k <= nb; k++) { h_off[k] = offsets[k] - base; }
-    for(u64 k = 0; k < nb; k++) { longest = std::max(longest, h_off[k + 1] - h_off[k]); }
-    TRY(d_text.alloc(bytes)); TRY(d_off.alloc((nb + 1) * sizeof(u64))); TRY(d_slots.alloc(2 * nb * sizeof(u64), true)); TRY(d_base.alloc((nb + 1) * sizeof(u64)));
-    if(bytes > 0) { HIP_TRY(hipMemcpyAsync(d_text.p, patterns + base, bytes, hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (nb + 1) * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    TRY(cur.reserve(nb));
+    TRY(stage(patterns, offsets, nb, 2 * nb));
+    TRY(cur.reserve(nb, who));
     LAUNCH("approx_roots", k_approx_roots, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, d_off.as<const u64>(), nb, x->n, approx_nodes(cur, nb));
     u64 count = nb, peak = nb;
-    nhits = 0;
     const u64 levels = std::max<u64>(longest, 1);                                               // an empty pattern's root becomes its hit in the first one
     for(u64 t = 0; t < levels && count > 0; t++)
     {
       const u64 nblocks = div_up(count, block_nodes);
-      if(2 * nblocks + 1 > totals_cap)
-      {
-        totals_cap = std::max<u64>(2 * nblocks + 1, 2 * totals_cap);
-        TRY(d_totals.alloc(totals_cap * sizeof(u64)));
-      }
-      u64* totals = d_totals.as<u64>();
-      TRY(level(false, v, bytes, nb, count, nblocks, 0, 0));
-      TRY(device_scan<0>(totals, totals, 2 * nblocks + 1));
-      TRY(fetch_u64(totals + nblocks, 0)); TRY(fetch_u64(totals + 2 * nblocks, 1));
-      HIP_TRY(hipStreamSynchronize(CTX.stream));
+      TRY(totals.reserve(2, nblocks));
+      TRY(level(false, v, nb, count, nblocks, 0, 0));
+      TRY(totals.scan_and_read(2, nblocks, 1));                                                 // the next frontier's size, and that plus the level's hits
       const u64 kept = CTX.host_scratch[0], both = CTX.host_scratch[1];
       if(kept > 5 * count || both < kept || both - kept > 5 * count)
       {
@@ -132,79 +92,38 @@ struct ApproxBatch
       }
       const u64 found = both - kept;
       t_approx_stats[0] += count; t_approx_stats[3] = std::max(t_approx_stats[3], t + 1);
-      if(kept > 0) { TRY(next.reserve(kept)); }
-      if(found > 0) { TRY(approx_keep(hits, nhits, nhits + found)); }
-      if(both > 0) { TRY(level(true, v, bytes, nb, count, nblocks, kept, found)); }
+      if(kept > 0) { TRY(next.reserve(kept, who)); }
+      if(found > 0) { TRY(hits.grow_keeping(nhits, nhits + found, who)); }
+      if(both > 0) { TRY(level(true, v, nb, count, nblocks, kept, found)); }
       if(found > 0)
       {
-        LAUNCH("approx_mark", k_approx_mark, div_up(found, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.code(), nhits, found, nb, first(), end(nb));
+        LAUNCH("approx_mark", k_approx_mark, div_up(found, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.array(2), nhits, found, nb, first(), end(nb));
         nhits += found;
       }
-      if(kept > 0) { cur.buf.swap(next.buf); std::swap(cur.cap, next.cap); }
+      if(kept > 0) { cur.swap(next); }
       count = kept; peak = std::max(peak, kept);
     }
     t_approx_stats[1] = std::max(t_approx_stats[1], peak); t_approx_stats[2] = std::max(t_approx_stats[2], nhits);
     LAUNCH("approx_cap", k_approx_cap, div_up(nb + 1, BLOCK_THREADS), BLOCK_THREADS, (const u64*)first(), (const u64*)end(nb), nb, max_hits, d_base.as<u64>());
-    TRY(device_scan<0>(d_base.as<const u64>(), d_base.as<u64>(), nb + 1));
-    HIP_TRY(hipMemcpyAsync(hit_offsets, d_base.p, (nb + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
-    kept_total = hit_offsets[nb];
-    if(kept_total > nhits) { return fail(BWTM_EINVAL, "bwtm_find_approx_batch: %llu hits kept of %llu found", (unsigned long long)kept_total, (unsigned long long)nhits); }
-    if(before != 0) { for(u64 k = 0; k <= nb; k++) { hit_offsets[k] += before; } }              // a later batch of the call
-    return BWTM_OK;
+    return finish_offsets(who, nb, before, hit_offsets);
   }
 
   // The kept hits of the batch search() has just seen, in pattern order, into the caller's arrays (any of them null).
-  int fill(u64 nb, u64* out_sp, u64* out_count, u8* out_mismatches)
+  int fill(u64 nb, const PatternHits& out)
   {
     if(kept_total == 0) { return BWTM_OK; }
     if(kept_total > (~0ull) / 24) { return fail(BWTM_ENOMEM, "bwtm_find_approx_batch: %llu hits do not fit", (unsigned long long)kept_total); }
     TRY(d_out.alloc(17 * kept_total));
     u64* o_sp = d_out.as<u64>(); u64* o_cnt = o_sp + kept_total; u8* o_mm = (u8*)(o_cnt + kept_total);
-    LAUNCH("approx_gather", k_approx_gather, div_up(nhits, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.sp(), (const u64*)hits.cnt(), (const u64*)hits.code(), nhits, nb,
+    LAUNCH("approx_gather", k_approx_gather, div_up(nhits, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.array(0), (const u64*)hits.array(1), (const u64*)hits.array(2), nhits, nb,
       (const u64*)first(), d_base.as<const u64>(), o_sp, o_cnt, o_mm, kept_total);
-    if(out_sp) { HIP_TRY(hipMemcpyAsync(out_sp, o_sp, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_count) { HIP_TRY(hipMemcpyAsync(out_count, o_cnt, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_mismatches) { HIP_TRY(hipMemcpyAsync(out_mismatches, o_mm, kept_total, hipMemcpyDeviceToHost, CTX.stream)); }
+    if(out.sp) { HIP_TRY(hipMemcpyAsync(out.sp, o_sp, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
+    if(out.count) { HIP_TRY(hipMemcpyAsync(out.count, o_cnt, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
+    if(out.cost) { HIP_TRY(hipMemcpyAsync(out.cost, o_mm, kept_total, hipMemcpyDeviceToHost, CTX.stream)); }
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers are reused
     return BWTM_OK;
   }
 };
-
-// First every batch is searched, so that hit_offsets is complete and the capacity is checked before anything else is written; then the
-// hits are gathered.  A call of one batch keeps its hit stream between the two; a call of several searches every batch a second time
-// (the streams of all batches do not stay anywhere: the memory is that of one batch).
-int approx_run(const bwtm_index* x, const u8* patterns, const u64* offsets, u64 count, u32 max_mismatches, u64 max_hits, u64* hit_offsets,
-               u64* out_sp, u64* out_count, u8* out_mismatches, u64 capacity)
-{
-  const u64 batch = std::min(approx_batch_size(), count);
-  const bool single = (batch >= count);
-  ApproxBatch b;
-  b.x = x; b.max_mismatches = max_mismatches; b.max_hits = max_hits;
-  for(u64 done = 0; done < count; done += batch)
-  {
-    TRY(b.search(patterns, offsets + done, std::min(batch, count - done), hit_offsets + done));
-  }
-  const u64 total = hit_offsets[count];
-  if((!out_sp && !out_count && !out_mismatches) || capacity == 0 || total == 0) { return BWTM_OK; }       // sizes only
-  if(capacity < total)
-  {
-    return fail(BWTM_EINVAL, "bwtm_find_approx_batch: capacity %llu is too small (%llu hits)", (unsigned long long)capacity, (unsigned long long)total);
-  }
-  const u64 s0 = t_approx_stats[0];
-  for(u64 done = 0; done < count; done += batch)
-  {
-    const u64 nb = std::min(batch, count - done);
-    const u64 at = hit_offsets[done];
-    if(!single)
-    {
-      TRY(b.search(patterns, offsets + done, nb, hit_offsets + done));
-      t_approx_stats[0] = s0;                                                                   // the same nodes a second time
-    }
-    TRY(b.fill(nb, (out_sp ? out_sp + at : nullptr), (out_count ? out_count + at : nullptr), (out_mismatches ? out_mismatches + at : nullptr)));
-  }
-  return BWTM_OK;
-}
 
 } // namespace
 
@@ -221,25 +140,9 @@ extern "C" int bwtm_find_approx_batch(const bwtm_index* x, const uint8_t* patter
   for(u32 j = 0; j < 4; j++) { t_approx_stats[j] = 0; }
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  for(u64 k = 0; k < count; k++)
-  {
-    if(offsets[k] > offsets[k + 1]) { return fail(BWTM_EINVAL, "bwtm_find_approx_batch: offsets must not decrease (pattern %llu)", (unsigned long long)k); }
-    const u64 len = offsets[k + 1] - offsets[k];
-    if(len > APPROX_MAX_LEN)
-    {
-      return fail(BWTM_EINVAL, "bwtm_find_approx_batch: pattern %llu has %llu symbols (at most %llu)", (unsigned long long)k, (unsigned long long)len, (unsigned long long)APPROX_MAX_LEN);
-    }
-    if(len > 0 && !patterns) { return fail(BWTM_EINVAL, "bwtm_find_approx_batch: null pattern text"); }
-    for(u64 p = offsets[k]; p < offsets[k + 1]; p++)
-    {
-      if(patterns[p] < 1 || patterns[p] > 5)
-      {
-        return fail(BWTM_EINVAL, "bwtm_find_approx_batch: pattern %llu holds the symbol %u at offset %llu (comp values 1..5)", (unsigned long long)k, (unsigned)patterns[p],
-          (unsigned long long)(p - offsets[k]));
-      }
-    }
-  }
-  const int rc = approx_run(x, patterns, offsets, count, max_mismatches, max_hits, hit_offsets, out_sp, out_count, out_mismatches, capacity);
+  TRY(validate_patterns("bwtm_find_approx_batch", patterns, offsets, count));
+  const int rc = pattern_run<ApproxBatch>("bwtm_find_approx_batch", t_approx_stats, x, patterns, offsets, count, max_mismatches, max_hits, hit_offsets,
+    PatternHits{out_sp, out_count, out_mismatches, nullptr}, capacity);
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.stream); }                                 // the half-built state goes back to the pool behind this
   return rc;
 }

@@ -6,8 +6,8 @@
 
       peak <= 392 P + 2^20 bytes                                       (every block below 512 MiB)
 
-  320 P  two frontiers of 40 bytes per node.  As in api/kmers.hip.h a frontier's capacity at least doubles when it grows, so the blocks
-         one frontier ever had -- which stay with the pool once given back -- hold fewer than 4 P nodes together.
+  320 P  two frontiers of 40 bytes per node, whose capacities at least double when they grow (api/frontier.hip.h: the blocks one frontier
+         ever had hold fewer than 4 P nodes together).
    40 P  the result at its exact size, when the last frontier's block is larger: the handle keeps 40 bytes per k-mer and nothing else.
     8 P  the per-workgroup totals of the split (32 bytes per 256 nodes, the same doubling) and the partial sums of their scan.
    24 P + 2^20  what the pool rounds up: a block of 1 MiB or more to 64 KiB, of 64 MiB or more to 2 MiB, a smaller one to 256 bytes
@@ -34,23 +34,7 @@ struct bwtm_kmer_join
 namespace
 {
 
-// One frontier: five arrays of `cap` entries in one block.
-struct KmerJoinFrontier
-{
-  DevBuf buf; u64 cap = 0;
-  u64* array(u32 which) const { return buf.as<u64>() + which * cap; }
-  KmerJoinNodes nodes() const { return KmerJoinNodes{array(0), array(1), array(2), array(3), array(4)}; }
-  // room for `need` nodes; the old contents are not kept
-  int reserve(u64 need)
-  {
-    if(need <= cap && buf.p) { return BWTM_OK; }
-    const u64 want = std::max<u64>(std::max<u64>(need, 2 * cap), 1);
-    if(want > (~0ull) / 40) { return fail(BWTM_ENOMEM, "bwtm_kmer_join_create: a frontier of %llu nodes does not fit", (unsigned long long)want); }
-    TRY(buf.alloc(5 * want * sizeof(u64)));
-    cap = want;
-    return BWTM_OK;
-  }
-};
+KmerJoinNodes kmer_join_nodes(const Frontier<5>& f) { return KmerJoinNodes{f.array(0), f.array(1), f.array(2), f.array(3), f.array(4)}; }
 
 bool kmer_join_keeps(u64 ca, u64 cb, const KmerJoinBounds& bd)
 {
@@ -62,8 +46,9 @@ int kmer_join_build(bwtm_kmer_join* kj, const bwtm_index* a, const bwtm_index* b
   const IndexView va = a->view(), vb = b->view();
   KmerJoinBounds inner = last;                                                                  // upper bounds cannot prune above level k
   inner.max_a = ~0ull; inner.max_b = ~0ull;
-  KmerJoinFrontier cur, next;
-  DevBuf totals; u64 totals_cap = 0;
+  const char* const who = "bwtm_kmer_join_create";
+  Frontier<5> cur, next;
+  LevelTotals totals;
   // level 1, from both C arrays
   u64 h_nodes[20]; u64 count = 0;
   for(u32 j = 0; j < 4; j++)
@@ -78,7 +63,7 @@ int kmer_join_build(bwtm_kmer_join* kj, const bwtm_index* a, const bwtm_index* b
   kj->levels[0] = count;
   if(count > 0)
   {
-    TRY(cur.reserve(count));
+    TRY(cur.reserve(count, who));
     for(u32 w = 0; w < 5; w++) { HIP_TRY(hipMemcpyAsync(cur.array(w), h_nodes + 4 * w, count * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // h_nodes is on the stack
   }
@@ -86,36 +71,24 @@ int kmer_join_build(bwtm_kmer_join* kj, const bwtm_index* a, const bwtm_index* b
   {
     const KmerJoinBounds& bd = (t + 1 < k ? inner : last);
     const u64 nblocks = div_up(count, (u64)BLOCK_THREADS);
-    if(4 * nblocks + 1 > totals_cap)
-    {
-      totals_cap = std::max<u64>(4 * nblocks + 1, 2 * totals_cap);
-      TRY(totals.alloc(totals_cap * sizeof(u64)));
-    }
-    LAUNCH("kmer_join_count", (k_kmer_join_level<false>), nblocks, BLOCK_THREADS, va, vb, skip, bd, t, cur.nodes(), count, nblocks, totals.as<u64>(), KmerJoinNodes{}, (u64)0);
-    TRY(device_scan<0>(totals.as<u64>(), totals.as<u64>(), 4 * nblocks + 1));
-    TRY(fetch_u64(totals.as<u64>() + 4 * nblocks, 0));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));
+    TRY(totals.reserve(4, nblocks));
+    LAUNCH("kmer_join_count", (k_kmer_join_level<false>), nblocks, BLOCK_THREADS, va, vb, skip, bd, t, kmer_join_nodes(cur), count, nblocks, totals.p(), KmerJoinNodes{}, (u64)0);
+    TRY(totals.scan_and_read(4, nblocks, 4));                                                   // the size of the next frontier
     const u64 kept = CTX.host_scratch[0];
     if(kept > 4 * count) { return fail(BWTM_EINVAL, "bwtm_kmer_join_create: level %u counted %llu children of %llu nodes", t + 1, (unsigned long long)kept, (unsigned long long)count); }
     kj->levels[t] = kept;
     if(kept > 0)
     {
-      TRY(next.reserve(kept));
-      LAUNCH("kmer_join_expand", (k_kmer_join_level<true>), nblocks, BLOCK_THREADS, va, vb, skip, bd, t, cur.nodes(), count, nblocks, totals.as<u64>(), next.nodes(), kept);
-      cur.buf.swap(next.buf); std::swap(cur.cap, next.cap);
+      TRY(next.reserve(kept, who));
+      LAUNCH("kmer_join_expand", (k_kmer_join_level<true>), nblocks, BLOCK_THREADS, va, vb, skip, bd, t, kmer_join_nodes(cur), count, nblocks, totals.p(), kmer_join_nodes(next), kept);
+      cur.swap(next);
     }
     count = kept;
   }
-  next.buf.release(); totals.release();
+  next.buf.release(); totals.buf.release();
   kj->distinct = count; kj->k = k;
   if(count == 0) { return BWTM_OK; }                                                            // the handle holds no block
-  if(cur.cap != count)                                                                          // the result at its exact size
-  {
-    KmerJoinFrontier exact;
-    TRY(exact.reserve(count));
-    for(u32 w = 0; w < 5; w++) { HIP_TRY(hipMemcpyAsync(exact.array(w), cur.array(w), count * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream)); }
-    cur.buf.swap(exact.buf); std::swap(cur.cap, exact.cap);
-  }
+  TRY(cur.shrink_to(count, who));                                                               // the result at its exact size
   kj->nodes.swap(cur.buf); kj->capacity = cur.cap;
   DevBuf d_stats;
   TRY(d_stats.alloc(KMER_JOIN_STATS * sizeof(u64), true));

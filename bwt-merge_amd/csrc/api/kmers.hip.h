@@ -6,10 +6,9 @@
 
       peak <= 240 P + 2^20 bytes                                       (every block below 512 MiB)
 
-  192 P  two frontiers of 24 bytes per node.  A level's size is known only after its count pass, and a block the pool has handed out and
-         taken back stays with the pool: a frontier that grew by a little every level would leave a block per level behind.  So a
-         frontier's capacity at least doubles when it grows: the blocks one frontier ever had hold fewer than 4 P nodes together.  (The
-         early levels grow fourfold and are allocated exactly; a deep level of a read collection hardly grows at all.)
+  192 P  two frontiers of 24 bytes per node, whose capacities at least double when they grow (api/frontier.hip.h: the blocks one frontier
+         ever had hold fewer than 4 P nodes together).  The early levels grow fourfold and are allocated exactly; a deep level of a read
+         collection hardly grows at all.
    24 P  the result at its exact size, when the last frontier's block is larger: the handle keeps 24 bytes per k-mer and nothing else.
     8 P  the per-workgroup totals of the split (32 bytes per 256 nodes, the same doubling) and the partial sums of their scan.
    16 P + 2^20  what the pool rounds up: a block of 1 MiB or more to 64 KiB, of 64 MiB or more to 2 MiB, a smaller one to 256 bytes.
@@ -36,42 +35,20 @@ struct bwtm_kmers
 namespace
 {
 
-// One frontier: three arrays of `cap` entries in one block.
-struct KmerFrontier
-{
-  DevBuf buf; u64 cap = 0;
-  u64* sp() const { return buf.as<u64>(); }
-  u64* cnt() const { return buf.as<u64>() + cap; }
-  u64* code() const { return buf.as<u64>() + 2 * cap; }
-  // room for `need` nodes; the old contents are not kept
-  int reserve(u64 need)
-  {
-    if(need <= cap && buf.p) { return BWTM_OK; }
-    const u64 want = std::max<u64>(std::max<u64>(need, 2 * cap), 1);
-    if(want > (~0ull) / 24) { return fail(BWTM_ENOMEM, "bwtm_kmers_create: a frontier of %llu nodes does not fit", (unsigned long long)want); }
-    TRY(buf.alloc(3 * want * sizeof(u64)));
-    cap = want;
-    return BWTM_OK;
-  }
-};
-
-// The two launches of a level and the scan between them; the size of the next frontier is in CTX.host_scratch[0] after the first half.
+// The two launches of a level over the frontier `in` (sp, count, code).
 template<bool QUAD>
-int kmers_level_count(const IndexView& v, u32 skip, u64 min_count, u32 t, const KmerFrontier& in, u64 count, u64 nblocks, u64* totals)
+int kmers_level_count(const IndexView& v, u32 skip, u64 min_count, u32 t, const Frontier<3>& in, u64 count, u64 nblocks, u64* totals)
 {
-  LAUNCH("kmer_count", (k_kmer_level<QUAD, false>), nblocks, BLOCK_THREADS, v, skip, min_count, t, (const u64*)in.sp(), (const u64*)in.cnt(), (const u64*)in.code(), count, nblocks,
+  LAUNCH("kmer_count", (k_kmer_level<QUAD, false>), nblocks, BLOCK_THREADS, v, skip, min_count, t, (const u64*)in.array(0), (const u64*)in.array(1), (const u64*)in.array(2), count, nblocks,
     totals, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (u64)0);
-  TRY(device_scan<0>(totals, totals, 4 * nblocks + 1));
-  TRY(fetch_u64(totals + 4 * nblocks, 0));
-  HIP_TRY(hipStreamSynchronize(CTX.stream));
   return BWTM_OK;
 }
 
 template<bool QUAD>
-int kmers_level_emit(const IndexView& v, u32 skip, u64 min_count, u32 t, const KmerFrontier& in, u64 count, u64 nblocks, u64* totals, const KmerFrontier& out, u64 kept)
+int kmers_level_emit(const IndexView& v, u32 skip, u64 min_count, u32 t, const Frontier<3>& in, u64 count, u64 nblocks, u64* totals, const Frontier<3>& out, u64 kept)
 {
-  LAUNCH("kmer_expand", (k_kmer_level<QUAD, true>), nblocks, BLOCK_THREADS, v, skip, min_count, t, (const u64*)in.sp(), (const u64*)in.cnt(), (const u64*)in.code(), count, nblocks,
-    totals, out.sp(), out.cnt(), out.code(), kept);
+  LAUNCH("kmer_expand", (k_kmer_level<QUAD, true>), nblocks, BLOCK_THREADS, v, skip, min_count, t, (const u64*)in.array(0), (const u64*)in.array(1), (const u64*)in.array(2), count, nblocks,
+    totals, out.array(0), out.array(1), out.array(2), kept);
   return BWTM_OK;
 }
 
@@ -84,8 +61,9 @@ int kmers_build(bwtm_kmers* km, const bwtm_index* x, u32 k, u32 skip, u64 min_co
 #endif
   const u64 block_nodes = (quad ? kmer_block_nodes<true>() : kmer_block_nodes<false>());
   const IndexView v = x->view();
-  KmerFrontier cur, next;
-  DevBuf totals; u64 totals_cap = 0;
+  const char* const who = "bwtm_kmers_create";
+  Frontier<3> cur, next;
+  LevelTotals totals;
   // level 1: the kept symbols that occur often enough
   u64 h_nodes[12]; u64 count = 0;
   for(u32 j = 0; j < 4; j++)
@@ -97,50 +75,37 @@ int kmers_build(bwtm_kmers* km, const bwtm_index* x, u32 k, u32 skip, u64 min_co
   km->levels[0] = count;
   if(count > 0)
   {
-    TRY(cur.reserve(count));
-    HIP_TRY(hipMemcpyAsync(cur.sp(), h_nodes, count * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(cur.cnt(), h_nodes + 4, count * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(cur.code(), h_nodes + 8, count * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
+    TRY(cur.reserve(count, who));
+    for(u32 w = 0; w < 3; w++) { HIP_TRY(hipMemcpyAsync(cur.array(w), h_nodes + 4 * w, count * sizeof(u64), hipMemcpyHostToDevice, CTX.stream)); }
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // h_nodes is on the stack
   }
   for(u32 t = 1; t < k && count > 0; t++)
   {
     const u64 nblocks = div_up(count, block_nodes);
-    if(4 * nblocks + 1 > totals_cap)
-    {
-      totals_cap = std::max<u64>(4 * nblocks + 1, 2 * totals_cap);
-      TRY(totals.alloc(totals_cap * sizeof(u64)));
-    }
+    TRY(totals.reserve(4, nblocks));
 #ifdef BWTM_DIAGNOSTICS
-    if(quad) { TRY(kmers_level_count<true>(v, skip, min_count, t, cur, count, nblocks, totals.as<u64>())); } else
+    if(quad) { TRY(kmers_level_count<true>(v, skip, min_count, t, cur, count, nblocks, totals.p())); } else
 #endif
-    { TRY(kmers_level_count<false>(v, skip, min_count, t, cur, count, nblocks, totals.as<u64>())); }
+    { TRY(kmers_level_count<false>(v, skip, min_count, t, cur, count, nblocks, totals.p())); }
+    TRY(totals.scan_and_read(4, nblocks, 4));                                                   // the size of the next frontier
     const u64 kept = CTX.host_scratch[0];
     if(kept > 4 * count) { return fail(BWTM_EINVAL, "bwtm_kmers_create: level %u counted %llu children of %llu nodes", t + 1, (unsigned long long)kept, (unsigned long long)count); }
     km->levels[t] = kept;
     if(kept > 0)
     {
-      TRY(next.reserve(kept));
+      TRY(next.reserve(kept, who));
 #ifdef BWTM_DIAGNOSTICS
-      if(quad) { TRY(kmers_level_emit<true>(v, skip, min_count, t, cur, count, nblocks, totals.as<u64>(), next, kept)); } else
+      if(quad) { TRY(kmers_level_emit<true>(v, skip, min_count, t, cur, count, nblocks, totals.p(), next, kept)); } else
 #endif
-      { TRY(kmers_level_emit<false>(v, skip, min_count, t, cur, count, nblocks, totals.as<u64>(), next, kept)); }
-      cur.buf.swap(next.buf); std::swap(cur.cap, next.cap);
+      { TRY(kmers_level_emit<false>(v, skip, min_count, t, cur, count, nblocks, totals.p(), next, kept)); }
+      cur.swap(next);
     }
     count = kept;
   }
-  next.buf.release(); totals.release();
+  next.buf.release(); totals.buf.release();
   km->distinct = count; km->k = k;
   if(count == 0) { return BWTM_OK; }                                                            // the handle holds no block
-  if(cur.cap != count)                                                                          // the result at its exact size
-  {
-    KmerFrontier exact;
-    TRY(exact.reserve(count));
-    HIP_TRY(hipMemcpyAsync(exact.sp(), cur.sp(), count * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(exact.cnt(), cur.cnt(), count * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-    HIP_TRY(hipMemcpyAsync(exact.code(), cur.code(), count * sizeof(u64), hipMemcpyDeviceToDevice, CTX.stream));
-    cur.buf.swap(exact.buf); std::swap(cur.cap, exact.cap);
-  }
+  TRY(cur.shrink_to(count, who));                                                               // the result at its exact size
   km->nodes.swap(cur.buf); km->capacity = cur.cap;
   DevBuf d_total;
   TRY(d_total.alloc(sizeof(u64), true));

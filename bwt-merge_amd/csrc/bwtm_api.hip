@@ -17,6 +17,8 @@
     api/sequences.hip.h sequences by id: lengths, offsets and text in batches of bounded device memory
     api/locate.hip.h    positions to (sequence id, offset): the locator's table, positions and ranges located in batches
     api/overlap.hip.h   suffix-prefix overlaps: one backward search per query, counted, then emitted and expanded through the locator's table
+    api/frontier.hip.h  the host side of the level scheme the next four share: the doubling frontier of parallel arrays, a level's totals with their
+                        scan and read-back, a batch of patterns with its hit stream and offsets, the two rounds of a pattern call
     api/kmers.hip.h     the distinct k-mers of an index with counts and ranges: the trie's levels on two ping-pong frontiers, the spectrum
     api/kmer_join.hip.h the k-mers of two indexes with their counts and insertion points in each: one joint walk, the summary of the result
     api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern
@@ -62,6 +64,7 @@ using namespace bwtm;
 #include "api/sequences.hip.h"
 #include "api/locate.hip.h"
 #include "api/overlap.hip.h"
+#include "api/frontier.hip.h"
 #include "api/kmers.hip.h"
 #include "api/kmer_join.hip.h"
 #include "api/approx.hip.h"

@@ -42,6 +42,9 @@
                        suffix-prefix overlaps: one backward search per query (the same reader, two records per step) whose rank(., 0)
                        pairs are intervals of the locator's table, counted, then emitted longest first and expanded to (id, length)
                        (kernels/overlap.hip.h; the overlap step of a string-graph assembler, no counterpart in the reference)
+    kernels/level.hip.h (no kernel): what the four level-wise trie walks below share -- the lane's ranks of a range (level_lane_ranks) and
+                       the stable placement of a level's children without atomics: count pass, one scan, expand pass (level_place,
+                       level_publish, level_slot)
     k_kmer_level<QUAD, EMIT>, k_kmer_sum, k_kmer_hist
                        the distinct k-mers with their counts: the suffix trie down to depth k, level by level, every level the stable
                        split by symbol of the one before (count pass, scan, expand-and-scatter pass), and the spectrum of the result
@@ -50,7 +53,7 @@
                        the k-mers of two indexes side by side: one joint walk down both suffix tries, a node a range in each index
                        (an insertion point where the string is absent), the same stable split per level, and the summary of the result
                        (kernels/kmer_join.hip.h; the first levels of the merger's own search, generalised; no counterpart in the reference)
-    k_approx_roots, k_approx_level<EMIT>, k_approx_mark, k_approx_cap, k_approx_gather
+    k_approx_roots, k_approx_level<QUAD, EMIT>, k_approx_mark, k_approx_cap, k_approx_gather
                        patterns with up to d substitutions: the backward search of a batch as one frontier of (range, pattern, symbols
                        left, mismatches spent), every level a count pass, a scan and an expand pass into the next frontier and the hit
                        stream, both in parent-then-symbol order; then every pattern's hits found by their neighbours and gathered
@@ -110,6 +113,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/sequences.hip.h"
 #include "kernels/locate.hip.h"
 #include "kernels/overlap.hip.h"
+#include "kernels/level.hip.h"
 #include "kernels/kmers.hip.h"
 #include "kernels/kmer_join.hip.h"
 #include "kernels/approx.hip.h"

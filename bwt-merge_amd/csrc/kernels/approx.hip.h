@@ -1,7 +1,7 @@
 /*
   kernels/approx.hip.h -- patterns with up to d substitutions: a backward search whose frontier carries ranges, so that the Hamming
   neighbours of a pattern share every prefix of the search and a branch dies when its range is empty.
-  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/kmers.hip.h whose level it follows); gfx950 only.
+  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/level.hip.h whose level it is); gfx950 only.
 */
 #pragma once
 
@@ -19,13 +19,9 @@
 // from their last symbol backwards -- the order of a depth-first search that tries the symbols 1..5 in turn.  A root with left == 0 (the
 // empty pattern) is a hit itself: it goes to the hit stream as it is.
 //
-// Two launches per level over the same frontier, and one scan between them (the shape of k_kmer_level):
-//   k_approx_level<QUAD, false>   totals[b] = children for the next frontier from workgroup b, totals[nblocks + b] = its hits,
-//                           totals[2 nblocks] = 0.  ONE exclusive scan over the 2 nblocks + 1 entries gives every workgroup its first slot
-//                           in both streams; totals[nblocks] is then the size of the next frontier and totals[2 nblocks] that size plus
-//                           the hits of the level, which the host reads back and allocates from.
-//   k_approx_level<QUAD, true>    computes the same children again and stores them at the workgroup's slot + the kept children of the lanes
-//                           before this one (ballots within a wave, wave totals through LDS): no atomic decides a position.
+// A level is the count pass, the scan and the expand pass of kernels/level.hip.h with two streams, the next frontier (0) and the hits (1):
+// after the scan totals[nblocks] is the size of the next frontier and totals[2 nblocks] that size plus the hits of the level, which the
+// host reads back and allocates from; the expand pass moves its hit slots from behind the next frontier to behind the batch's earlier hits.
 //
 // QUAD = false: one lane per node, the whole record in its registers (k_kmer_level<false, .>'s way); 256 nodes per workgroup.  The default.
 // QUAD = true:  four lanes per node on the record reader of kernels/quad.hip.h: lane q loads chunk q, every rank is a quad sum, every lane
@@ -50,37 +46,7 @@ struct ApproxNodes
   u64* sp; u64* cnt; u64* meta; u64 capacity;
 };
 
-// rank(sp, .) and rank(e, .) of one lane, sp < e <= n.  sp == 0: no load.  e == n: from C.  Same record: one load.
-__device__ inline void approx_lane_ranks(const IndexView& x, const u64* sC, u64 sp, u64 e, u64 rs[6], u64 re[6])
-{
-  u32 w[16];
-  const bool at_end = (e == x.n);
-  u64 loaded = ~0ull;
-#pragma unroll
-  for(u32 c = 1; c < 6; c++) { rs[c] = 0; }
-  if(sp > 0)
-  {
-    loaded = sp >> REC_SHIFT;
-    load_record(x.recs, loaded, w);
-    const u64* s = x.sup + (sp >> SUPER_SHIFT) * SUP_STRIDE;
-    const u32 js = (u32)(sp & (REC_POS - 1));
-#pragma unroll
-    for(u32 c = 1; c < 6; c++) { rs[c] = s[c] + rec_header(w, c) + rec_count(w, c, js); }
-  }
-  if(at_end)
-  {
-#pragma unroll
-    for(u32 c = 1; c < 6; c++) { re[c] = sC[c + 1] - sC[c]; }
-    return;
-  }
-  if((e >> REC_SHIFT) != loaded) { load_record(x.recs, e >> REC_SHIFT, w); }
-  const u64* s = x.sup + (e >> SUPER_SHIFT) * SUP_STRIDE;
-  const u32 je = (u32)(e & (REC_POS - 1));
-#pragma unroll
-  for(u32 c = 1; c < 6; c++) { re[c] = s[c] + rec_header(w, c) + rec_count(w, c, je); }
-}
-
-// The same for the four lanes of a quad (lane q of it): chunk q of each record, every rank a quad sum.  Quad-uniform.
+// level_lane_ranks for the four lanes of a quad (lane q of it): chunk q of each record, every rank a quad sum.  Quad-uniform.
 __device__ inline void approx_quad_ranks(const IndexView& x, const u64* sC, u32 q, u64 sp, u64 e, u64 rs[6], u64 re[6])
 {
   const bool at_end = (e == x.n), from_zero = (sp == 0);
@@ -148,7 +114,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_approx_level(IndexView x, con
         const u32 want = text[at];
         u64 rs[6], re[6];
         if(QUAD) { approx_quad_ranks(x, sC, q, sp, sp + cnt, rs, re); }
-        else { approx_lane_ranks(x, sC, sp, sp + cnt, rs, re); }
+        else { level_lane_ranks(x, sC, sp, sp + cnt, rs, re); }
 #pragma unroll
         for(u32 j = 0; j < 5; j++)
         {
@@ -165,36 +131,16 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_approx_level(IndexView x, con
   const u32 wave = threadIdx.x >> 6;
   const bool stands = (!QUAD || q == 0);                                    // this lane stands for its node in the ballots
   const u64 below = (1ull << (QUAD ? (lane_id() & ~3u) : lane_id())) - 1ull;
-  const u64 hit_lanes = __ballot(stands && is_hit);
-  const u64 mine = (is_hit ? hit_lanes : ~hit_lanes);
-  u32 wave_next = 0, wave_hits = 0, before = 0;
-#pragma unroll
-  for(u32 j = 0; j < 5; j++)
-  {
-    const u64 ballot = __ballot(stands && ((keep >> j) & 1u));
-    wave_next += (u32)__builtin_popcountll(ballot & ~hit_lanes);
-    wave_hits += (u32)__builtin_popcountll(ballot & hit_lanes);
-    before += (u32)__builtin_popcountll(ballot & mine & below);
-  }
+  u32 wave_next, wave_hits, before_next, before_hits;                       // a lane's kept children all go to one of the two streams
+  level_place<5>(is_hit ? 0u : keep, stands, below, &wave_next, &before_next);
+  level_place<5>(is_hit ? keep : 0u, stands, below, &wave_hits, &before_hits);
   if(lane_id() == 0) { s_wave[wave][0] = wave_next; s_wave[wave][1] = wave_hits; }
   __syncthreads();
-  if(!EMIT)
-  {
-    if(threadIdx.x < 2)
-    {
-      u32 sum = 0;
-#pragma unroll
-      for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { sum += s_wave[w][threadIdx.x]; }
-      totals[(u64)threadIdx.x * nblocks + blockIdx.x] = sum;
-    }
-    if(blockIdx.x == 0 && threadIdx.x == 0) { totals[2 * nblocks] = 0; }    // the scan runs over 2 nblocks + 1 entries
-    return;
-  }
+  if(!EMIT) { level_publish<2>(s_wave, totals, nblocks); return; }
   if(keep == 0) { return; }
   const ApproxNodes& out = (is_hit ? hits : next);
-  u64 slot = (is_hit ? hit_base + (totals[nblocks + blockIdx.x] - totals[nblocks]) : totals[blockIdx.x]) + before;
-#pragma unroll
-  for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { if(w < wave) { slot += s_wave[w][is_hit ? 1 : 0]; } }
+  u64 slot = level_slot<2>(s_wave, totals, nblocks, is_hit ? 1u : 0u, wave) + (is_hit ? before_hits : before_next);
+  if(is_hit) { slot = hit_base + (slot - totals[nblocks]); }                // the scan ran through both streams; the hit stream continues at hit_base
 #pragma unroll
   for(u32 j = 0; j < 5; j++)
   {

@@ -1,7 +1,7 @@
 /*
   kernels/edit.hip.h -- patterns within edit distance e (insertions, deletions, substitutions): the frontier search of kernels/approx.hip.h
   whose node carries a band of the edit-distance matrix instead of one mismatch counter, so that its hits appear over several levels.
-  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/approx.hip.h whose ranks and streams it uses); gfx950 only.
+  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/approx.hip.h whose streams it uses); gfx950 only.
 */
 #pragma once
 
@@ -25,12 +25,10 @@
 // stays grouped by pattern and, within a pattern, ascending when the strings are compared from their last symbol backwards; the hits
 // of one pattern and one length stand next to each other in the stream, in that order.
 //
-// Two launches per level over the same frontier and one scan between them, exactly as k_approx_level: the count pass leaves the
-// workgroup's kept children in totals[b] and its hits in totals[nblocks + b]; the expand pass stores at the workgroup's slot + the
-// kept children (the hits) of the lanes before this one -- ballots within a wave, wave totals through LDS, no atomic decides a position.
-// One lane per node, 256 nodes per workgroup.
+// A level is the count pass, the scan and the expand pass of kernels/level.hip.h with k_approx_level's two streams, the next frontier and
+// the hits; here a lane may bring children to both.  One lane per node, 256 nodes per workgroup.
 // No load leaves the index or the batch's text, whatever the nodes hold: sp and sp + count are clamped to n first, a node with count == 0
-// loads nothing, rank(0, .) and rank(n, .) are not loads (approx_lane_ranks), a pattern number beyond the batch expands nothing, every index
+// loads nothing, rank(0, .) and rank(n, .) are not loads (level_lane_ranks), a pattern number beyond the batch expands nothing, every index
 // into the text is clamped into it before the load.  Every store is checked against the capacity the host allocated from the read-back.
 // There is no loop whose length depends on data.
 
@@ -120,7 +118,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_edit_level(IndexView x, const
           }
         }
         u64 rs[6], re[6];
-        approx_lane_ranks(x, sC, sp, sp + cnt, rs, re);
+        level_lane_ranks(x, sC, sp, sp + cnt, rs, re);
         const u32 top = (u32)(t + 1 < EDIT_SAT ? t + 1 : EDIT_SAT);         // D_cW[0]
 #pragma unroll
         for(u32 j = 0; j < 5; j++)
@@ -157,40 +155,15 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_edit_level(IndexView x, const
   // both streams in lane order within a wave, wave order within a workgroup, workgroup order through the scan; a lane's children in symbol order
   const u32 wave = threadIdx.x >> 6;
   const u64 below = (1ull << lane_id()) - 1ull;
-  u32 wave_next = 0, wave_hits = 0, before_next = 0, before_hits = 0;
-#pragma unroll
-  for(u32 j = 0; j < 5; j++)
-  {
-    const u64 ballot = __ballot((keep >> j) & 1u);
-    wave_next += (u32)__builtin_popcountll(ballot);
-    before_next += (u32)__builtin_popcountll(ballot & below);
-  }
-#pragma unroll
-  for(u32 j = 0; j < 6; j++)
-  {
-    const u64 ballot = __ballot((hit >> j) & 1u);
-    wave_hits += (u32)__builtin_popcountll(ballot);
-    before_hits += (u32)__builtin_popcountll(ballot & below);
-  }
+  u32 wave_next, wave_hits, before_next, before_hits;
+  level_place<5>(keep, true, below, &wave_next, &before_next);
+  level_place<6>(hit, true, below, &wave_hits, &before_hits);
   if(lane_id() == 0) { s_wave[wave][0] = wave_next; s_wave[wave][1] = wave_hits; }
   __syncthreads();
-  if(!EMIT)
-  {
-    if(threadIdx.x < 2)
-    {
-      u32 sum = 0;
-#pragma unroll
-      for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { sum += s_wave[w][threadIdx.x]; }
-      totals[(u64)threadIdx.x * nblocks + blockIdx.x] = sum;
-    }
-    if(blockIdx.x == 0 && threadIdx.x == 0) { totals[2 * nblocks] = 0; }    // the scan runs over 2 nblocks + 1 entries
-    return;
-  }
+  if(!EMIT) { level_publish<2>(s_wave, totals, nblocks); return; }
   if(keep == 0 && hit == 0) { return; }
-  u64 slot = totals[blockIdx.x] + before_next;
-  u64 hslot = hit_base + (totals[nblocks + blockIdx.x] - totals[nblocks]) + before_hits;
-#pragma unroll
-  for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { if(w < wave) { slot += s_wave[w][0]; hslot += s_wave[w][1]; } }
+  u64 slot = level_slot<2>(s_wave, totals, nblocks, 0, wave) + before_next;
+  u64 hslot = hit_base + (level_slot<2>(s_wave, totals, nblocks, 1, wave) - totals[nblocks]) + before_hits;
   if(hit & 1u)
   {
     if(hslot < hits.capacity) { nt_store(hits.sp + hslot, sp); nt_store(hits.cnt + hslot, cnt); nt_store(hits.meta + hslot, edit_hit_meta(pattern, 0, m)); }

@@ -1,6 +1,6 @@
 /*
   kernels/kmer_join.hip.h -- the k-mers of TWO collections side by side: one joint walk down the suffix tries of two indexes, one level per step.
-  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/kmers.hip.h whose lane ranks and code it uses); gfx950 only.
+  Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/kmers.hip.h whose code it uses); gfx950 only.
 */
 #pragma once
 
@@ -10,7 +10,7 @@
 // and sp_x is its INSERTION POINT: the number of suffixes of x that are smaller than the string.  The LF formula gives both alike,
 //     sp_x' = C_x[c] + rank_x(sp_x, c),   cnt_x' = rank_x(sp_x + cnt_x, c) - rank_x(sp_x, c)
 // (the suffixes smaller than cX are those that start with a smaller symbol and those cY with Y < X), so a side whose count has fallen to 0
-// is walked on like the other one: there sp == e, kmer_lane_ranks loads one record, every lane of a wave still does the same thing, and
+// is walked on like the other one: there sp == e, level_lane_ranks loads one record, every lane of a wave still does the same thing, and
 // the result says where the k-mer would stand in that index -- which makes sp_a + sp_b its position in the merged index.
 //
 // A child is kept when cnt_a >= min_a, cnt_b >= min_b and cnt_a + cnt_b >= min_sum (min_sum >= 1: a string neither index holds is never
@@ -36,7 +36,7 @@ __device__ inline void kmer_join_side(const IndexView& x, const u64* sC, u32 ski
   if(sp > x.n) { sp = x.n; }
   if(cnt > x.n - sp) { cnt = x.n - sp; }
   u64 rs[6], re[6];
-  kmer_lane_ranks(x, sC, sp, sp + cnt, rs, re);
+  level_lane_ranks(x, sC, sp, sp + cnt, rs, re);
 #pragma unroll
   for(u32 j = 0; j < 4; j++)
   {
@@ -73,37 +73,25 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_kmer_join_level(IndexView xa,
       if(ca >= bd.min_a && ca <= bd.max_a && cb >= bd.min_b && cb <= bd.max_b && ca + cb >= bd.min_sum) { keep |= 1u << j; }
     }
   }
-  // the stable split of k_kmer_level: per symbol, the lanes of a wave in lane order, the waves of a workgroup in wave order, the workgroups through the scan
+  // the stable split of k_kmer_level: one stream per symbol (kernels/level.hip.h)
   const u32 wave = threadIdx.x >> 6;
   const u64 below = (1ull << lane_id()) - 1ull;
-  u64 ballot[4];
+  u32 before[4];
 #pragma unroll
-  for(u32 j = 0; j < 4; j++) { ballot[j] = __ballot((keep >> j) & 1u); }
-  if(lane_id() == 0)
+  for(u32 j = 0; j < 4; j++)
   {
-#pragma unroll
-    for(u32 j = 0; j < 4; j++) { s_wave[wave][j] = (u32)__builtin_popcountll(ballot[j]); }
+    u32 wave_total;
+    level_place<1>(keep >> j, true, below, &wave_total, &before[j]);
+    if(lane_id() == 0) { s_wave[wave][j] = wave_total; }
   }
   __syncthreads();
-  if(!EMIT)
-  {
-    if(threadIdx.x < 4)
-    {
-      u32 sum = 0;
-#pragma unroll
-      for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { sum += s_wave[w][threadIdx.x]; }
-      totals[(u64)threadIdx.x * nblocks + blockIdx.x] = sum;
-    }
-    if(blockIdx.x == 0 && threadIdx.x == 0) { totals[4 * nblocks] = 0; }    // the scan runs over 4 nblocks + 1 entries: the last one becomes the total
-    return;
-  }
+  if(!EMIT) { level_publish<4>(s_wave, totals, nblocks); return; }
 #pragma unroll
   for(u32 j = 0; j < 4; j++)
   {
     if((keep >> j) & 1u)
     {
-      u64 slot = totals[(u64)j * nblocks + blockIdx.x] + (u64)__builtin_popcountll(ballot[j] & below);
-      for(u32 w = 0; w < wave; w++) { slot += s_wave[w][j]; }
+      const u64 slot = level_slot<4>(s_wave, totals, nblocks, j, wave) + before[j];
       if(slot < capacity)
       {
         nt_store(out.sp_a + slot, aspc[j]); nt_store(out.cnt_a + slot, acnt[j]);

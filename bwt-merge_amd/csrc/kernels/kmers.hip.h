@@ -16,14 +16,8 @@
 // parent order, then those of the second, ...  LF is monotone per symbol, so it is sorted again, and the parents' records are read in
 // ascending order.
 //
-// Two launches per level over the same frontier, and one scan between them:
-//   k_kmer_level<QUAD, false>   totals[j * nblocks + b] = kept children of symbol j in workgroup b (symbol-major: ONE exclusive scan over
-//                               the 4 nblocks + 1 entries gives every workgroup its first slot per symbol, and the last entry the size
-//                               of the next frontier, which the host reads once per level and allocates from)
-//   k_kmer_level<QUAD, true>    computes the same children again (the ranks are not stored: 64 more bytes per node would be written and
-//                               read where one or two records are re-read in order) and stores the kept ones at
-//                               totals[j * nblocks + b] + kept ones of j in the lanes before this one
-// Both take the ranks the same way, so the second finds what the first counted; a store is still checked against the capacity.
+// A level is the count pass, the scan and the expand pass of kernels/level.hip.h with one stream per symbol (symbol-major totals): the last
+// entry of the scan is the size of the next frontier, which the host reads once per level and allocates from.
 //
 // QUAD = false: one lane per node, the whole record in its registers (index_ranks' way, k_find_batch's shape); 256 nodes per workgroup.
 //               The default: a frontier is sorted by sp, so neighbouring lanes read the same or the next record and the loads of a wave
@@ -45,31 +39,6 @@ template<bool QUAD> constexpr u32 kmer_block_nodes() { return (QUAD ? BLOCK_THRE
 
 // The comp value of the j-th kept symbol (j = 0..3): 1..5 without skip, ascending.
 __host__ __device__ inline u32 kmer_comp(u32 j, u32 skip) { return j + 1 + (j + 1 >= skip ? 1u : 0u); }
-
-// rank(sp, .) and rank(e, .) of one lane, sp <= e <= n.  e == n: from C.  Same record: one load.
-__device__ inline void kmer_lane_ranks(const IndexView& x, const u64* sC, u64 sp, u64 e, u64 rs[6], u64 re[6])
-{
-  u32 w[16];
-  load_record(x.recs, sp >> REC_SHIFT, w);
-  const u64* s = x.sup + (sp >> SUPER_SHIFT) * SUP_STRIDE;
-  const u32 js = (u32)(sp & (REC_POS - 1));
-#pragma unroll
-  for(u32 c = 1; c < 6; c++) { rs[c] = s[c] + rec_header(w, c) + rec_count(w, c, js); }
-  if(e == x.n)
-  {
-#pragma unroll
-    for(u32 c = 1; c < 6; c++) { re[c] = sC[c + 1] - sC[c]; }
-    return;
-  }
-  if((e >> REC_SHIFT) != (sp >> REC_SHIFT))
-  {
-    load_record(x.recs, e >> REC_SHIFT, w);
-    s = x.sup + (e >> SUPER_SHIFT) * SUP_STRIDE;
-  }
-  const u32 je = (u32)(e & (REC_POS - 1));
-#pragma unroll
-  for(u32 c = 1; c < 6; c++) { re[c] = s[c] + rec_header(w, c) + rec_count(w, c, je); }
-}
 
 // EMIT == false: totals[j * nblocks + blockIdx.x] = kept children of symbol j among this workgroup's nodes, and totals[4 * nblocks] = 0.
 // EMIT == true:  totals as the exclusive scan left them; the kept children go to out_*[..], never at or beyond `capacity`.
@@ -112,7 +81,7 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_kmer_level(IndexView x, u32 s
     else
     {
       u64 rs[6], re[6];
-      kmer_lane_ranks(x, sC, sp, e, rs, re);
+      level_lane_ranks(x, sC, sp, e, rs, re);
 #pragma unroll
       for(u32 j = 0; j < 4; j++)
       {
@@ -123,37 +92,25 @@ __global__ void __launch_bounds__(BLOCK_THREADS) k_kmer_level(IndexView x, u32 s
       }
     }
   }
-  // the stable split: per symbol, the lanes of a wave in lane order, the waves of a workgroup in wave order, the workgroups through the scan
+  // the stable split: one stream per symbol (kernels/level.hip.h)
   const u32 wave = threadIdx.x >> 6;
   const u64 below = (1ull << lane_id()) - 1ull;
-  u64 ballot[4];
+  u32 before[4];
 #pragma unroll
-  for(u32 j = 0; j < 4; j++) { ballot[j] = __ballot((keep >> j) & 1u); }
-  if(lane_id() == 0)
+  for(u32 j = 0; j < 4; j++)
   {
-#pragma unroll
-    for(u32 j = 0; j < 4; j++) { s_wave[wave][j] = (u32)__builtin_popcountll(ballot[j]); }
+    u32 wave_total;
+    level_place<1>(keep >> j, true, below, &wave_total, &before[j]);
+    if(lane_id() == 0) { s_wave[wave][j] = wave_total; }
   }
   __syncthreads();
-  if(!EMIT)
-  {
-    if(threadIdx.x < 4)
-    {
-      u32 sum = 0;
-#pragma unroll
-      for(u32 w = 0; w < BLOCK_THREADS / WAVE; w++) { sum += s_wave[w][threadIdx.x]; }
-      totals[(u64)threadIdx.x * nblocks + blockIdx.x] = sum;
-    }
-    if(blockIdx.x == 0 && threadIdx.x == 0) { totals[4 * nblocks] = 0; }    // the scan runs over 4 nblocks + 1 entries: the last one becomes the total
-    return;
-  }
+  if(!EMIT) { level_publish<4>(s_wave, totals, nblocks); return; }
 #pragma unroll
   for(u32 j = 0; j < 4; j++)
   {
     if((keep >> j) & 1u)
     {
-      u64 slot = totals[(u64)j * nblocks + blockIdx.x] + (u64)__builtin_popcountll(ballot[j] & below);
-      for(u32 w = 0; w < wave; w++) { slot += s_wave[w][j]; }
+      const u64 slot = level_slot<4>(s_wave, totals, nblocks, j, wave) + before[j];
       if(slot < capacity)
       {
         nt_store(out_sp + slot, csp[j]); nt_store(out_cnt + slot, ccnt[j]); nt_store(out_code + slot, ((u64)j << (2 * t)) | code);
