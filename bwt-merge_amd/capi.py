@@ -165,6 +165,14 @@ SYMBOLS = [
     ("bwtm_kmer_join_levels", C.c_int, [vp, p_u64]),
     ("bwtm_kmer_join_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64, p_u64, p_u64]),
     ("bwtm_kmer_join_summary", C.c_int, [vp, p_u64]),
+    ("bwtm_corrector_create", C.c_int, [vp, C.c_uint32, u64, C.POINTER(vp)]),
+    ("bwtm_corrector_free", None, [vp]),
+    ("bwtm_corrector_solid", u64, [vp]),
+    ("bwtm_corrector_bytes", u64, [vp]),
+    ("bwtm_corrector_k", C.c_uint32, [vp]),
+    ("bwtm_correct_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, p_u8, p_u8, p_u32]),
+    ("bwtm_correct_sequences", C.c_int, [vp, vp, p_u64, u64, u64, u64, C.c_uint32, p_u64, p_u8, u64, p_u8, p_u32]),
+    ("bwtm_correct_stats", C.c_int, [p_u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -926,6 +934,97 @@ class Kmers:
         hist = np.zeros(max(int(bins), 0), dtype=np.uint64)
         check(lib().bwtm_kmers_histogram(self.h, int(bins), hist.ctypes.data_as(p_u64)))
         return hist
+
+    def corrector(self, threshold, skip=5):
+        """The solid k-mers (count >= threshold) as a lookup table for error correction (bwtm_corrector_create); skip = the comp of N,
+        the one the k-mers were made with.  The corrector copies what it needs: these k-mers may be freed at once."""
+        self._live()
+        return Corrector(self, threshold, skip)
+
+
+CORRECT_CLEAN, CORRECT_CORRECTED, CORRECT_FAILED, CORRECT_SHORT = 0, 1, 2, 3
+CORRECT_STATS = ("lookups", "rounds", "max_edits", "batches")
+
+
+class Corrector:
+    """The solid k-mers of a spectrum on the device, and the correction of reads against them (handle on bwtm_corrector)."""
+
+    def __init__(self, kmers, threshold, skip=5):
+        out = vp()
+        check(lib().bwtm_corrector_create(kmers.h, int(skip), int(threshold), C.byref(out)))
+        self.h = out
+        self.skip, self.threshold = int(skip), max(int(threshold), 1)
+
+    solid = property(lambda s: int(lib().bwtm_corrector_solid(s.h)))
+    nbytes = property(lambda s: int(lib().bwtm_corrector_bytes(s.h)))
+    k = property(lambda s: int(lib().bwtm_corrector_k(s.h)))
+
+    def free(self):
+        if self.h:
+            lib().bwtm_corrector_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h:
+            raise BwtmError("the corrector has been freed")
+
+    def correct(self, patterns, max_rounds=10):
+        """Reads from the host (bwtm_correct_batch): a list of sequences of comp values 1..5.  Returns (list of uint8 arrays, status
+        uint8 [count], edits uint32 [count]); status is one of CORRECT_CLEAN / _CORRECTED / _FAILED / _SHORT."""
+        self._live()
+        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lens)
+        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+        text, tp = _u8(text)
+        out = np.zeros(max(text.size, 1), dtype=np.uint8)
+        status = np.zeros(len(patterns), dtype=np.uint8)
+        edits = np.zeros(len(patterns), dtype=np.uint32)
+        check(lib().bwtm_correct_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_rounds), out.ctypes.data_as(p_u8),
+                                       status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+        return [out[int(offsets[j]): int(offsets[j + 1])] for j in range(len(patterns))], status, edits
+
+    def correct_sequences(self, index, ids=None, first=0, count=None, max_len=0, max_rounds=10, text=True):
+        """Reads of an index, extracted and corrected on the device (bwtm_correct_sequences); ids / first / count / max_len as in
+        Index.sequences.  Returns (offsets uint64 [count + 1], text uint8 or None, status, edits).  text=False: one status call.
+        Otherwise the sizing call of bwtm_sequences_extract, then the filling call."""
+        self._live()
+        ip = None
+        if ids is not None:
+            ids, ip = _u64(ids)
+            count = ids.size
+        elif count is None:
+            count = max(index.sequences - int(first), 0)
+        count = int(count)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        status = np.zeros(count, dtype=np.uint8)
+        edits = np.zeros(count, dtype=np.uint32)
+        args = (self.h, index.h, ip, int(first), count, int(max_len), int(max_rounds), offsets.ctypes.data_as(p_u64))
+        if not text:
+            check(lib().bwtm_correct_sequences(*args, None, 0, status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+            return offsets, None, status, edits
+        check(lib().bwtm_sequences_extract(index.h, ip, int(first), count, int(max_len), offsets.ctypes.data_as(p_u64), None, 0))     # the size
+        out = np.zeros(int(offsets[-1]), dtype=np.uint8)
+        check(lib().bwtm_correct_sequences(*args, out.ctypes.data_as(p_u8) if out.size else None, out.size, status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+        return offsets, out, status, edits
+
+    @staticmethod
+    def correct_stats():
+        return correct_stats()
+
+
+def correct_stats():
+    """What the calling thread's last correct call did (bwtm_correct_stats): table lookups, rounds run over all reads, the most edits in one
+    read, batches."""
+    stats = np.zeros(4, dtype=np.uint64)
+    check(lib().bwtm_correct_stats(stats.ctypes.data_as(p_u64)))
+    return dict(zip(CORRECT_STATS, (int(v) for v in stats)))
 
 
 KMER_JOIN_NO_BOUND = (1 << 64) - 1

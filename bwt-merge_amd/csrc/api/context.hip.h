@@ -112,6 +112,7 @@ struct Tuning
   long long locate_batch = 1ll << 20;     // bwtm_locator_create / bwtm_locate_*: sequences / hits per batch (at most 2^28; bounds the device memory beyond the index and the table)
   long long overlap_batch = 1ll << 20;    // bwtm_overlap_*: queries per batch (at most 2^28; bounds the device memory beyond the index and the table: text, interval records, one batch of hits)
   long long approx_batch = 1ll << 16;     // bwtm_find_approx_batch: patterns per batch (at most 2^28; bounds the device memory beyond the index: a frontier's size is known only once it has been counted)
+  long long correct_batch = 1ll << 20;    // bwtm_correct_*: reads per batch (at most 2^28; bounds the device memory beyond the table and the index: two copies of the text, offsets, status, edits)
   long long ingest_verify = 0;            // 1 = the builder checks every leaf's suffix order against the reads (one extra pass of gathers per leaf)
 #ifdef BWTM_DIAGNOSTICS
   long long walk_emit = 0;       // 0 = real emit; 1 / 2 timing-only variants of the emit (see diagnostics.hip.h)
@@ -123,6 +124,7 @@ struct Tuning
   long long overlap_kernel = 0;  // 0 = four lanes per query (default), 1 = one lane per query (k_find_batch's shape): the same results
   long long approx_kernel = 0;   // 0 = one lane per node of the bounded-mismatch search (default), 1 = four lanes per node on the same record reader: the same results
   long long kmers_kernel = 0;    // 0 = one lane per trie node (default), 1 = four lanes per node on the record reader of kernels/quad.hip.h: the same results
+  long long correct_kernel = 0;  // 0 = one wave per read of the error correction (default), 1 = one lane per read: the same results
 #endif
 };
 Tuning g_tune;
@@ -735,6 +737,7 @@ int tune_set(const char* key, long long value)
   else if(k == "locate_batch") { g_tune.locate_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "overlap_batch") { g_tune.overlap_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "approx_batch") { g_tune.approx_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 16)); }
+  else if(k == "correct_batch") { g_tune.correct_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }
   else if(k == "recs_uniform") { g_tune.recs_uniform = (value > 0 ? 1 : (value < 0 ? -1 : 0)); }
   else if(k == "recs_window") { g_tune.recs_window = (value == 8192 || value == 16384 || value == 32768 ? value : 0); }
@@ -751,6 +754,7 @@ int tune_set(const char* key, long long value)
   else if(k == "overlap_kernel") { g_tune.overlap_kernel = (value == 1 ? 1 : 0); }
   else if(k == "approx_kernel") { g_tune.approx_kernel = (value == 1 ? 1 : 0); }
   else if(k == "kmers_kernel") { g_tune.kmers_kernel = (value == 1 ? 1 : 0); }
+  else if(k == "correct_kernel") { g_tune.correct_kernel = (value == 1 ? 1 : 0); }
 #endif
   else { return fail(BWTM_EINVAL, "bwtm_tune: unknown key %s", key); }
   return BWTM_OK;

@@ -23,6 +23,8 @@
     api/kmer_join.hip.h the k-mers of two indexes with their counts and insertion points in each: one joint walk, the summary of the result
     api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern
     api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length
+    api/correct.hip.h   k-mer error correction of reads: the solid k-mers of a spectrum as a sorted table with a bucket directory, a wave per read,
+                        on patterns from the host or on sequences extracted on the device, in batches of bounded device memory
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -69,3 +71,4 @@ using namespace bwtm;
 #include "api/kmer_join.hip.h"
 #include "api/approx.hip.h"
 #include "api/edit.hip.h"
+#include "api/correct.hip.h"

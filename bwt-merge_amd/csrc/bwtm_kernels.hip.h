@@ -63,6 +63,10 @@
                        column around its depth), a child kept for the next frontier and / or a hit, independently, so that a pattern's
                        hits appear over 2 e + 1 levels; then marked and gathered per pattern and length
                        (kernels/edit.hip.h; no counterpart in the reference)
+    k_correct_flag, k_correct_compact, k_correct_dir, k_correct_wave
+                       k-mer error correction of reads: the codes of the solid k-mers compacted out of a spectrum, a bucket directory over
+                       their top bits, and one wave per read that looks its windows up 64 at a time, finds the uncovered positions from a
+                       ballot and substitutes one symbol per round (kernels/correct.hip.h; no counterpart in the reference)
 */
 #pragma once
 
@@ -118,6 +122,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/kmer_join.hip.h"
 #include "kernels/approx.hip.h"
 #include "kernels/edit.hip.h"
+#include "kernels/correct.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

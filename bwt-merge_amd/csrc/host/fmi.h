@@ -336,7 +336,57 @@ public:
   const size_type k, skip;
 
 private:
+  friend class Corrector;
   bwtm_kmers* handle = nullptr;
+};
+
+// K-mer error correction of reads against the solid k-mers of a spectrum (bwtm_corrector_create): the k-mers of count >= threshold, copied
+// out of `kmers`, which may be destroyed at once.  A read is made to consist of solid k-mers by single substitutions, one per round, at
+// most max_rounds of them (the rule: include/bwtm.h); status is one of BWTM_CORRECT_*.
+class Corrector
+{
+public:
+  typedef BWT::size_type size_type;
+
+  Corrector(const Kmers& kmers, size_type threshold) : k(kmers.k), skip(kmers.skip)
+  {
+    gpuCheck(bwtm_corrector_create(kmers.handle, (uint32_t)std::min<size_type>(kmers.skip, ~(uint32_t)0), threshold, &this->handle), "Corrector::Corrector()");
+  }
+  ~Corrector() { bwtm_corrector_free(this->handle); }
+  Corrector(const Corrector&) = delete; Corrector& operator=(const Corrector&) = delete;
+
+  size_type solid() const { return bwtm_corrector_solid(this->handle); }
+  size_type bytes() const { return bwtm_corrector_bytes(this->handle); }
+
+  // Reads from the host, laid out as for FMI::findApprox: read j = text[offsets[j] .. offsets[j + 1]), comp values.  corrected has the layout of text.
+  void correct(const std::vector<byte_type>& text, const std::vector<uint64_t>& offsets, size_type max_rounds, std::vector<byte_type>& corrected,
+               std::vector<byte_type>& status, std::vector<uint32_t>& edits) const
+  {
+    const size_type count = (offsets.empty() ? 0 : offsets.size() - 1);
+    corrected.assign(text.size(), 0); status.assign(count, 0); edits.assign(count, 0);
+    gpuCheck(bwtm_correct_batch(this->handle, text.data(), offsets.data(), count, (uint32_t)std::min<size_type>(max_rounds, ~(uint32_t)0), corrected.data(), status.data(),
+      edits.data()), "Corrector::correct()");
+  }
+
+  // The sequences ids.first .. ids.second of fmi, extracted and corrected on the device: sequence j is text[offsets[j] .. offsets[j + 1]).
+  // The index goes to the device if it is not there, and stays.
+  void sequences(const FMI& fmi, range_type ids, size_type max_rounds, std::vector<size_type>& offsets, std::vector<byte_type>& text, std::vector<byte_type>& status,
+                 std::vector<uint32_t>& edits, size_type max_len = 0) const
+  {
+    const size_type count = (ids.second >= ids.first ? ids.second - ids.first + 1 : 0);
+    offsets.assign(count + 1, 0); text.clear(); status.assign(count, 0); edits.assign(count, 0);
+    if(count == 0) { return; }
+    bwtm_index* ix = fmi.bwt.onDevice(fmi.alpha.C);
+    gpuCheck(bwtm_sequences_extract(ix, nullptr, ids.first, count, max_len, offsets.data(), nullptr, 0), "Corrector::sequences()");       // the size
+    text.resize(offsets[count]);
+    gpuCheck(bwtm_correct_sequences(this->handle, ix, nullptr, ids.first, count, max_len, (uint32_t)std::min<size_type>(max_rounds, ~(uint32_t)0), offsets.data(),
+      text.data(), text.size(), status.data(), edits.data()), "Corrector::sequences()");
+  }
+
+  const size_type k, skip;
+
+private:
+  bwtm_corrector* handle = nullptr;
 };
 
 // The k-mers of two FMIs' collections side by side, ascending, on the device (bwtm_kmer_join_create): every kept k-mer with its count and

@@ -30,4 +30,15 @@ int bwtm_locate_ranges(const bwtm_locator*, const uint64_t*, const uint64_t*, ui
 int bwtm_overlap_batch(const bwtm_locator*, const uint8_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
 int bwtm_overlap_sequences(const bwtm_locator*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t*, uint64_t*, uint64_t*, uint64_t) { return BWTM_ENODEV; }
 
+// the Corrector of fmi.h
+int bwtm_corrector_create(const bwtm_kmers*, uint32_t, uint64_t, bwtm_corrector** out) { *out = nullptr; return BWTM_ENODEV; }
+void bwtm_corrector_free(bwtm_corrector*) {}
+uint64_t bwtm_corrector_solid(const bwtm_corrector*) { return 0; }
+uint64_t bwtm_corrector_bytes(const bwtm_corrector*) { return 0; }
+int bwtm_correct_batch(const bwtm_corrector*, const uint8_t*, const uint64_t*, uint64_t, uint32_t, uint8_t*, uint8_t*, uint32_t*) { return BWTM_ENODEV; }
+int bwtm_correct_sequences(const bwtm_corrector*, const bwtm_index*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint32_t, uint64_t*, uint8_t*, uint64_t, uint8_t*, uint32_t*)
+{
+  return BWTM_ENODEV;
+}
+
 }

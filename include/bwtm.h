@@ -356,6 +356,69 @@ int bwtm_kmer_join_download(const bwtm_kmer_join* join, uint64_t first, uint64_t
    occurrences in a of the first class, stats[4] = those in b of the second, stats[5], stats[6] = those in a and in b of the third */
 int bwtm_kmer_join_summary(const bwtm_kmer_join* join, uint64_t stats[7]);
 
+/* K-mer error correction of reads against the spectrum, the step of a string-graph assembler between counting k-mers and computing
+   overlaps: every read is made to consist of SOLID k-mers by single substitutions, on the device.  k (1..32), `skip` (the comp of N)
+   and the codes are those of bwtm_kmers_create; the kept alphabet is the four comp values other than skip.  threshold t >= 1 (0 is
+   taken as 1); max_rounds R, 0 <= R <= 65535.
+   A window of k symbols is solid when it holds no skip symbol and its k-mer has count >= t in the table.  Position i of a read of m
+   symbols is COVERED when some solid window that starts at o contains it, max(0, i - k + 1) <= o <= min(i, m - k).  The rule for a
+   read S:
+     1. m < k: status SHORT, text unchanged, edits 0.
+     2. r = 0, edits = 0, W a copy of S.  Repeat:
+        a. every position of W covered: stop, status CLEAN if edits == 0, else CORRECTED; the text is W.
+        b. r == R: stop with FAILED.  Otherwise r += 1.
+        c. the uncovered positions i in ascending order; for each the window start o = max(0, i - k + 1) and after it
+           o = min(i, m - k) if that differs.  The candidates are the kept symbols c != W[i] for which the window at o with c
+           written at i is solid (a skip symbol elsewhere in the window: none).  The first (i, o) with EXACTLY ONE candidate sets
+           W[i] = c, edits += 1, and the next round begins.
+        d. no (i, o) had exactly one candidate: stop with FAILED.
+     3. FAILED returns the original text S and edits 0: nothing of a partial correction leaves the call.
+   One substitution per round; W[i] may be skip itself, so an N is corrected like any other symbol; reads are independent of each
+   other.  Reverse complements are not looked at: an index that holds both strands gives them.
+   The corrector COPIES the codes of the k-mers of count >= threshold out of the k-mer handle, which may be freed at once, and builds
+   a bucket directory over their top bits: with S = bwtm_corrector_solid and D = min(2 k, 24, max(1, ceil(log2 S))), bucket b is the
+   range of codes whose top D of their 2 k used bits equal b, and the handle holds 8 max(S, 1) + 8 (2^D + 1) bytes plus what the pool
+   rounds up (a block of 1 MiB or more to 64 KiB, of 64 MiB or more to 2 MiB, a smaller one to 256 bytes; two blocks; a block of 512 MiB or
+   more, S above 2^26, is made of whole chunks of 1 GiB: bwtm_corrector_bytes reports what is held).  While it is
+   created, 8 bytes per k-mer of the k-mer handle are held besides.  A k-mer handle created with a min_count above threshold simply
+   lacks the k-mers below min_count: they are not solid.  `skip` MUST be the skip the k-mer handle was created with: the handle does
+   not record it, so a different value cannot be refused, and it would read every code in another alphabet.  An empty table (S == 0) is valid: every read of k symbols or more FAILS.
+   Both correct calls work in batches of bwtm_tune("correct_batch") reads (default 2^20, at most 2^28).  Device memory of a call
+   beyond the table and the index, with B = reads and T = bytes of text of the largest batch: at most 17/8 T + 27 (B + 1) + 2^16
+   bytes while every block stays below 512 MiB (api/correct.hip.h derives it): the batch's text and its working copy, offsets,
+   status, edits and, for bwtm_correct_sequences, the extract stage of bwtm_sequences_extract.
+   BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument, skip outside 1..5, max_rounds > 65535, offsets that
+   decrease, a symbol outside 1..5, a window of an index, an id >= sequences, a sequence longer than max_len, a corrector and an
+   index of different contexts, a capacity that is too small. */
+#define BWTM_CORRECT_CLEAN 0
+#define BWTM_CORRECT_CORRECTED 1
+#define BWTM_CORRECT_FAILED 2
+#define BWTM_CORRECT_SHORT 3
+typedef struct bwtm_corrector bwtm_corrector;
+int bwtm_corrector_create(const bwtm_kmers* kmers, uint32_t skip, uint64_t threshold, bwtm_corrector** out);
+void bwtm_corrector_free(bwtm_corrector* corrector);
+uint64_t bwtm_corrector_solid(const bwtm_corrector* corrector);    /* k-mers of count >= threshold */
+uint64_t bwtm_corrector_bytes(const bwtm_corrector* corrector);    /* device bytes the handle holds */
+uint32_t bwtm_corrector_k(const bwtm_corrector* corrector);
+/* Reads from the host, laid out as for bwtm_find_batch: read j = patterns[offsets[j] .. offsets[j + 1]), comp values 1..5, a read
+   may be empty.  out_text has the input's layout (the same offsets); out_status[j] is one of BWTM_CORRECT_*, out_edits[j] the
+   substitutions made in read j.  Any of the three outputs may be NULL. */
+int bwtm_correct_batch(const bwtm_corrector* corrector, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
+                       uint32_t max_rounds, uint8_t* out_text, uint8_t* out_status, uint32_t* out_edits);
+/* Reads of an index, extracted and corrected on the device; ids / first_id / count / max_len / offsets / text / capacity as in
+   bwtm_sequences_extract.  offsets, text, out_status and out_edits may be NULL in any combination.  text == NULL or capacity == 0 is
+   a status call: the correction still runs, offsets, status and edits are filled, no text comes back.  Otherwise capacity >=
+   offsets[count] (BWTM_EINVAL if not): max_len and the capacity are checked before anything is written, so a refused call leaves
+   offsets, text, status and edits as they were (size the text with a status call, or with bwtm_sequences_extract); nothing behind
+   offsets[count] is touched.  A call of more than one batch walks every sequence twice (once for the lengths, once for the
+   text). */
+int bwtm_correct_sequences(const bwtm_corrector* corrector, const bwtm_index* index, const uint64_t* ids, uint64_t first_id,
+                           uint64_t count, uint64_t max_len, uint32_t max_rounds, uint64_t* offsets /* count + 1 */,
+                           uint8_t* text, uint64_t capacity, uint8_t* out_status, uint32_t* out_edits);
+/* What the calling thread's last correct call did: stats[0] = table lookups, stats[1] = rounds run over all reads, stats[2] = the
+   most edits in one read, stats[3] = batches. */
+int bwtm_correct_stats(uint64_t stats[4]);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
