@@ -141,6 +141,9 @@ SYMBOLS = [
     ("bwtm_find_approx_stats", C.c_int, [p_u64]),
     ("bwtm_find_edit_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, u64, p_u64, p_u64, p_u64, p_u8, p_u32, u64]),
     ("bwtm_find_edit_stats", C.c_int, [p_u64]),
+    ("bwtm_matching_stats_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u32, p_u64, p_u64]),
+    ("bwtm_mem_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, p_u64, p_u32, p_u32, p_u64, p_u64, u64]),
+    ("bwtm_mem_stats", C.c_int, [p_u64]),
     ("bwtm_extract", C.c_int, [vp, u64, u64, p_u8]),
     ("bwtm_sequences_extract", C.c_int, [vp, p_u64, u64, u64, u64, p_u64, p_u8, u64]),
     ("bwtm_locator_create", C.c_int, [vp, u64, C.POINTER(vp)]),
@@ -831,6 +834,45 @@ class Index:
                                              edits.ctypes.data_as(p_u8), lengths.ctypes.data_as(p_u32), total))
         return hit_offsets, sp, count, edits, lengths
 
+    def matching_stats(self, patterns):
+        """Matching statistics of a list of patterns (bwtm_matching_stats_batch).  Returns (lengths, sp, count), arrays over all symbols of
+        the patterns in order: the entry of symbol i of pattern k, at sum(len(patterns[:k])) + i, is the longest match that ends with that
+        symbol, lengths symbols long, and its range [sp, sp + count - 1]; (0, 0, 0) when the symbol alone does not occur."""
+        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lens)
+        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+        text, tp = _u8(text)
+        total = int(offsets[-1])
+        lengths = np.zeros(total, dtype=np.uint32)
+        sp = np.zeros(total, dtype=np.uint64)
+        count = np.zeros(total, dtype=np.uint64)
+        check(lib().bwtm_matching_stats_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), lengths.ctypes.data_as(p_u32),
+                                              sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64)))
+        return lengths, sp, count
+
+    def mems(self, patterns, min_length=1):
+        """Maximal exact matches of a list of patterns (bwtm_mem_batch).  Returns (hit_offsets [count + 1], begin, length, sp, count): the
+        MEMs of pattern k are [hit_offsets[k], hit_offsets[k + 1]), begins (and ends) ascending; MEM h is patterns[k][begin[h]: begin[h] +
+        length[h]], length[h] >= min_length, and occurs at the positions [sp[h], sp[h] + count[h] - 1].  One sizing call, then the filling call."""
+        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(lens)
+        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+        text, tp = _u8(text)
+        hit_offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+        check(lib().bwtm_mem_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_length), hit_offsets.ctypes.data_as(p_u64),
+                                   None, None, None, None, 0))
+        total = int(hit_offsets[-1])
+        begin = np.zeros(total, dtype=np.uint32)
+        length = np.zeros(total, dtype=np.uint32)
+        sp = np.zeros(total, dtype=np.uint64)
+        count = np.zeros(total, dtype=np.uint64)
+        if total > 0:
+            check(lib().bwtm_mem_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_length), hit_offsets.ctypes.data_as(p_u64),
+                                       begin.ctypes.data_as(p_u32), length.ctypes.data_as(p_u32), sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64), total))
+        return hit_offsets, begin, length, sp, count
+
     def extract(self, first, count):
         out = np.zeros(count, dtype=np.uint8)
         check(lib().bwtm_extract(self.h, first, count, out.ctypes.data_as(p_u8)))
@@ -1161,6 +1203,14 @@ class Locator:
         hit_offsets, sp, count, edits, lengths = self.index.find_edit(patterns, max_edits, max_hits)
         occ_offsets, ids, offs = self.locate_ranges(sp, sp + count - np.uint64(1))
         return hit_offsets, sp, count, edits, lengths, occ_offsets, ids, offs
+
+    def locate_mems(self, patterns, min_length, max_hits=0):
+        """Every occurrence of every maximal exact match of every pattern: Index.mems, then locate_ranges on the MEMs' ranges.  Returns
+        (hit_offsets, begin, length, sp, count) of mems and (occ_offsets, ids, offsets) of locate_ranges over the MEMs (max_hits caps the
+        occurrences of a MEM): MEM h occurs at offsets[j] of sequence ids[j] for j in [occ_offsets[h], occ_offsets[h + 1])."""
+        hit_offsets, begin, length, sp, count = self.index.mems(patterns, min_length)
+        occ_offsets, ids, offs = self.locate_ranges(sp, sp + count - np.uint64(1), max_hits)
+        return hit_offsets, begin, length, sp, count, occ_offsets, ids, offs
 
     def _overlap_calls(self, call, count, max_hits):
         """The sizing call, then the real one: call(hit_offsets, ids, lengths, capacity) is one of the two C calls with its queries bound."""
@@ -1622,6 +1672,14 @@ def find_edit_stats():
     stats = np.zeros(4, dtype=np.uint64)
     check(lib().bwtm_find_edit_stats(stats.ctypes.data_as(p_u64)))
     return dict(expanded=int(stats[0]), frontier_peak=int(stats[1]), batch_hits=int(stats[2]), levels=int(stats[3]))
+
+
+def mem_stats():
+    """What the calling thread's last Index.matching_stats or Index.mems call did (bwtm_mem_stats; of its second, filling call when there
+    were MEMs): LF steps taken, tasks run, MEMs before min_length, batches."""
+    stats = np.zeros(4, dtype=np.uint64)
+    check(lib().bwtm_mem_stats(stats.ctypes.data_as(p_u64)))
+    return dict(steps=int(stats[0]), tasks=int(stats[1]), mems=int(stats[2]), batches=int(stats[3]))
 
 
 def pool_poison_stats():

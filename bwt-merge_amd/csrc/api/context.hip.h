@@ -111,6 +111,7 @@ struct Tuning
   long long extract_batch = 1ll << 20;    // bwtm_sequences_extract: sequences per batch (bounds the device memory of the call beyond the index)
   long long locate_batch = 1ll << 20;     // bwtm_locator_create / bwtm_locate_*: sequences / hits per batch (at most 2^28; bounds the device memory beyond the index and the table)
   long long overlap_batch = 1ll << 20;    // bwtm_overlap_*: queries per batch (at most 2^28; bounds the device memory beyond the index and the table: text, interval records, one batch of hits)
+  long long mem_batch = 1ll << 20;        // bwtm_matching_stats_batch / bwtm_mem_batch: patterns per batch (at most 2^28; bounds the device memory beyond the index: text, 20 bytes of statistics and 8 of flags per symbol, one batch of MEMs)
   long long approx_batch = 1ll << 16;     // bwtm_find_approx_batch: patterns per batch (at most 2^28; bounds the device memory beyond the index: a frontier's size is known only once it has been counted)
   long long correct_batch = 1ll << 20;    // bwtm_correct_*: reads per batch (at most 2^28; bounds the device memory beyond the table and the index: two copies of the text, offsets, status, edits)
   long long ingest_verify = 0;            // 1 = the builder checks every leaf's suffix order against the reads (one extra pass of gathers per leaf)
@@ -125,6 +126,7 @@ struct Tuning
   long long approx_kernel = 0;   // 0 = one lane per node of the bounded-mismatch search (default), 1 = four lanes per node on the same record reader: the same results
   long long kmers_kernel = 0;    // 0 = one lane per trie node (default), 1 = four lanes per node on the record reader of kernels/quad.hip.h: the same results
   long long correct_kernel = 0;  // 0 = one wave per read of the error correction (default), 1 = one lane per read: the same results
+  long long mem_kernel = 0;      // 0 = four lanes per PATTERN of the MEM search, ends descending (k_mem_pattern, default), 1 = four lanes per END and the rule on the lengths (k_ms_scan + k_mem_flag): the same results
 #endif
 };
 Tuning g_tune;
@@ -736,6 +738,7 @@ int tune_set(const char* key, long long value)
   else if(k == "extract_batch") { g_tune.extract_batch = (value > 0 ? value : (1ll << 20)); }
   else if(k == "locate_batch") { g_tune.locate_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "overlap_batch") { g_tune.overlap_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
+  else if(k == "mem_batch") { g_tune.mem_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "approx_batch") { g_tune.approx_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 16)); }
   else if(k == "correct_batch") { g_tune.correct_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }
@@ -755,6 +758,7 @@ int tune_set(const char* key, long long value)
   else if(k == "approx_kernel") { g_tune.approx_kernel = (value == 1 ? 1 : 0); }
   else if(k == "kmers_kernel") { g_tune.kmers_kernel = (value == 1 ? 1 : 0); }
   else if(k == "correct_kernel") { g_tune.correct_kernel = (value == 1 ? 1 : 0); }
+  else if(k == "mem_kernel") { g_tune.mem_kernel = (value == 1 ? 1 : 0); }
 #endif
   else { return fail(BWTM_EINVAL, "bwtm_tune: unknown key %s", key); }
   return BWTM_OK;

@@ -25,6 +25,8 @@
     api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length
     api/correct.hip.h   k-mer error correction of reads: the solid k-mers of a spectrum as a sorted table with a bucket directory, a wave per read,
                         on patterns from the host or on sequences extracted on the device, in batches of bounded device memory
+    api/mem.hip.h       matching statistics and maximal exact matches of patterns: one backward search per symbol of a batch's text; for the MEMs a quad
+                        per pattern that flags the ends that give one, two scans and one emit, in batches of bounded device memory
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -72,3 +74,4 @@ using namespace bwtm;
 #include "api/approx.hip.h"
 #include "api/edit.hip.h"
 #include "api/correct.hip.h"
+#include "api/mem.hip.h"

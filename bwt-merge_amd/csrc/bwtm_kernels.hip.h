@@ -42,6 +42,12 @@
                        suffix-prefix overlaps: one backward search per query (the same reader, two records per step) whose rank(., 0)
                        pairs are intervals of the locator's table, counted, then emitted longest first and expanded to (id, length)
                        (kernels/overlap.hip.h; the overlap step of a string-graph assembler, no counterpart in the reference)
+    k_ms_scan, k_mem_pattern, k_mem_emit (k_mem_flag)
+                       matching statistics and maximal exact matches of patterns: one backward search per (pattern, end) on the same
+                       reader, which keeps the last range that is not empty; for the MEMs one quad per pattern, ends descending, that
+                       flags the ends whose search gets below the begin of the search before, the flags scanned into slots and emitted
+                       as (begin, length, range); k_mem_flag, the same flags from the lengths of k_ms_scan, is the A/B partner
+                       (kernels/mem.hip.h; the seeds of seed-and-extend, no counterpart in the reference)
     kernels/level.hip.h (no kernel): what the four level-wise trie walks below share -- the lane's ranks of a range (level_lane_ranks) and
                        the stable placement of a level's children without atomics: count pass, one scan, expand pass (level_place,
                        level_publish, level_slot)
@@ -117,6 +123,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/sequences.hip.h"
 #include "kernels/locate.hip.h"
 #include "kernels/overlap.hip.h"
+#include "kernels/mem.hip.h"
 #include "kernels/level.hip.h"
 #include "kernels/kmers.hip.h"
 #include "kernels/kmer_join.hip.h"

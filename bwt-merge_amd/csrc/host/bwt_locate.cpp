@@ -8,7 +8,12 @@
   With -d N the search allows up to N substitutions (bwtm_find_approx_batch: no reverse complements) and every line gains a
   fourth column, the number of places in which the occurrence differs from the pattern; -x then bounds the occurrences written per
   matched string.  With -e N it allows up to N insertions, deletions and substitutions (bwtm_find_edit_batch) and every line gains
-  two columns, the edit distance of the occurrence from the pattern and its length.  Without -d and -e the output is what it always was.
+  two columns, the edit distance of the occurrence from the pattern and its length.  With -M N the pattern is not searched as a whole:
+  its maximal exact matches of at least N symbols are (bwtm_mem_batch: the substrings of the pattern that occur and lie in no longer
+  one that occurs), every one located, and every line is
+      pattern_number <TAB> sequence <TAB> offset <TAB> begin <TAB> length
+  with the match pattern[begin .. begin + length) at `offset` of `sequence`; -x then bounds the occurrences written per match.  The
+  lines of a pattern are sorted by (begin, sequence, offset).  Without -d, -e and -M the output is what it always was.
   Sequence k of an index built by bwt_ingest, or merged from such indexes by bwt_merge, is read k of the input(s) in order.
 */
 #include <unistd.h>
@@ -30,7 +35,9 @@ static void printUsage()
   std::cerr << "  -d N           Allow up to N substitutions, 0 to 8, and write the mismatches of every hit as a fourth column;" << std::endl;
   std::cerr << "                 -x then applies to every matched string (default: exact search, three columns)" << std::endl;
   std::cerr << "  -e N           Allow up to N edits (insertions, deletions, substitutions), 0 to 7, and write the edit distance and the" << std::endl;
-  std::cerr << "                 length of every hit as a fourth and fifth column; -x as with -d; not together with -d" << std::endl << std::endl;
+  std::cerr << "                 length of every hit as a fourth and fifth column; -x as with -d; not together with -d" << std::endl;
+  std::cerr << "  -M N           Locate the maximal exact matches of at least N symbols (N >= 1) of every pattern and write the begin and the" << std::endl;
+  std::cerr << "                 length of the match as a fourth and fifth column; -x then applies to every match; not together with -d or -e" << std::endl << std::endl;
   printFormats(std::cerr);
 }
 
@@ -52,9 +59,9 @@ int main(int argc, char** argv)
 
   int device = 0;
   std::string input_tag = NativeFormat::tag();
-  size_type max_len = 0, max_hits = 0, mismatches = 0, edits = 0;
-  bool approx = false, edit = false;
-  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:d:e:")) != -1; )
+  size_type max_len = 0, max_hits = 0, mismatches = 0, edits = 0, min_length = 0;
+  bool approx = false, edit = false, mem = false;
+  for(int c = 0; (c = getopt(argc, argv, "g:i:m:x:d:e:M:")) != -1; )
   {
     switch(c)
     {
@@ -73,17 +80,23 @@ int main(int argc, char** argv)
       edit = true; edits = std::stoull(optarg);
       if(edits > 7) { std::cerr << "bwt_locate: -e takes 0 to 7 edits" << std::endl; std::exit(EXIT_FAILURE); }
       break;
+    case 'M':
+      mem = true; min_length = std::stoull(optarg);
+      if(min_length < 1) { std::cerr << "bwt_locate: -M takes a length of at least 1" << std::endl; std::exit(EXIT_FAILURE); }
+      break;
     default: std::exit(EXIT_FAILURE);
     }
   }
+  if(mem && (approx || edit)) { std::cerr << "bwt_locate: -M cannot be used together with -d or -e" << std::endl; std::exit(EXIT_FAILURE); }
   if(approx && edit) { std::cerr << "bwt_locate: -d and -e cannot be used together" << std::endl; std::exit(EXIT_FAILURE); }
   if(optind + 2 >= argc) { std::cerr << "bwt_locate: Input, pattern and output files must be specified" << std::endl; std::exit(EXIT_FAILURE); }
   std::string input_name = argv[optind], pattern_name = argv[optind + 1], output_name = argv[optind + 2];
   std::cout << "Input:    " << input_name << " (" << input_tag << ")" << std::endl;
   std::cout << "Patterns: " << pattern_name << std::endl;
-  std::cout << "Output:   " << output_name << (edit ? " (pattern, sequence, offset, edits, length)" : approx ? " (pattern, sequence, offset, mismatches)" : " (pattern, sequence, offset)") << std::endl;
+  std::cout << "Output:   " << output_name << (mem ? " (pattern, sequence, offset, begin, length)" : edit ? " (pattern, sequence, offset, edits, length)" : approx ? " (pattern, sequence, offset, mismatches)" : " (pattern, sequence, offset)") << std::endl;
   if(approx) { std::cout << "Search:   up to " << mismatches << " substitutions" << std::endl; }
   if(edit) { std::cout << "Search:   up to " << edits << " edits" << std::endl; }
+  if(mem) { std::cout << "Search:   maximal exact matches of at least " << min_length << " symbols" << std::endl; }
   std::cout << std::endl;
 
   double start = readTimer();
@@ -166,6 +179,35 @@ int main(int argc, char** argv)
         {
           lines += std::to_string(k); lines += '\t'; lines += std::to_string(row.first.first); lines += '\t'; lines += std::to_string(row.first.second); lines += '\t';
           lines += std::to_string(row.second.first); lines += '\t'; lines += std::to_string(row.second.second); lines += '\n';
+        }
+        out.write(lines.data(), (std::streamsize)lines.size());
+      }
+    }
+    else if(mem)
+    {
+      // every maximal exact match of a pattern is a range of its own: located like the others, its begin and length written with every occurrence
+      std::vector<size_type> mem_offsets; std::vector<FMI::MEM> mems;
+      fmi.mems(text, offsets, min_length, mem_offsets, mems);
+      std::vector<range_type> ranges(mems.size());
+      for(size_type s = 0; s < mems.size(); s++) { ranges[s] = mems[s].range; }
+      Locator locator(fmi, max_len);
+      std::vector<size_type> hit_offsets; std::vector<Locator::hit_type> hits;
+      locator.locate(ranges, hit_offsets, hits, max_hits);
+      total = hits.size();
+      std::string lines;
+      for(size_type k = 0; k < patterns.size(); k++)
+      {
+        if(mem_offsets[k + 1] == mem_offsets[k]) { continue; }
+        found++;
+        lines.clear();
+        for(size_type s = mem_offsets[k]; s < mem_offsets[k + 1]; s++)                          // begins ascending
+        {
+          std::sort(hits.begin() + hit_offsets[s], hits.begin() + hit_offsets[s + 1]);
+          for(size_type h = hit_offsets[s]; h < hit_offsets[s + 1]; h++)
+          {
+            lines += std::to_string(k); lines += '\t'; lines += std::to_string(hits[h].first); lines += '\t'; lines += std::to_string(hits[h].second); lines += '\t';
+            lines += std::to_string(mems[s].begin); lines += '\t'; lines += std::to_string(mems[s].length); lines += '\n';
+          }
         }
         out.write(lines.data(), (std::streamsize)lines.size());
       }

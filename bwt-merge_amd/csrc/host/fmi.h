@@ -201,6 +201,60 @@ public:
     for(size_type h = 0; h < total; h++) { hits[h].range = range_type(sp[h], sp[h] + len[h] - 1); hits[h].edits = ed[h]; hits[h].length = lengths[h]; }
   }
 
+  // The longest match that ends with one symbol of a pattern: its length (0: the symbol alone does not occur) and its range, as find()
+  // returns it (empty when the length is 0).
+  struct MatchStat
+  {
+    size_type length; range_type range;
+  };
+
+  // Matching statistics of patterns given as comp values 1..5: pattern k is text[offsets[k] .. offsets[k + 1]), and stats holds one
+  // entry per symbol of the text, at offsets[k] + i - offsets[0] for symbol i of pattern k.  On the device (bwtm_matching_stats_batch).
+  // The index goes to the device if it is not there, and stays.
+  void matchingStats(const std::vector<byte_type>& text, const std::vector<uint64_t>& offsets, std::vector<MatchStat>& stats) const
+  {
+    const size_type count = (offsets.empty() ? 0 : offsets.size() - 1);
+    stats.clear();
+    const size_type total = (count == 0 ? 0 : offsets[count] - offsets[0]);
+    if(total == 0) { return; }
+    bwtm_index* ix = bwt.onDevice(alpha.C);
+    std::vector<uint32_t> lengths(total); std::vector<uint64_t> sp(total), len(total);
+    gpuCheck(bwtm_matching_stats_batch(ix, text.data(), offsets.data(), count, lengths.data(), sp.data(), len.data()), "FMI::matchingStats()");
+    stats.resize(total);
+    for(size_type h = 0; h < total; h++)
+    {
+      stats[h].length = lengths[h];
+      stats[h].range = (lengths[h] > 0 ? range_type(sp[h], sp[h] + len[h] - 1) : range_type(1, 0));
+    }
+  }
+
+  // A maximal exact match of a pattern: pattern[begin .. begin + length) occurs, and no longer substring of the pattern that contains
+  // it does; its range, as find() returns it.
+  struct MEM
+  {
+    size_type begin, length; range_type range;
+  };
+
+  // The maximal exact matches of at least min_length (>= 1) symbols of patterns given as comp values 1..5: pattern k is
+  // text[offsets[k] .. offsets[k + 1]), its MEMs are mems[hit_offsets[k] .. hit_offsets[k + 1]), begins and ends ascending.  On the
+  // device (bwtm_mem_batch: a sizing call, then the filling one).  The index goes to the device if it is not there, and stays.
+  void mems(const std::vector<byte_type>& text, const std::vector<uint64_t>& offsets, size_type min_length, std::vector<size_type>& hit_offsets,
+    std::vector<MEM>& mems) const
+  {
+    const size_type count = (offsets.empty() ? 0 : offsets.size() - 1);
+    hit_offsets.assign(count + 1, 0); mems.clear();
+    if(count == 0) { return; }
+    bwtm_index* ix = bwt.onDevice(alpha.C);
+    const uint32_t least = (uint32_t)std::min<size_type>(min_length, ~(uint32_t)0);
+    gpuCheck(bwtm_mem_batch(ix, text.data(), offsets.data(), count, least, hit_offsets.data(), nullptr, nullptr, nullptr, nullptr, 0), "FMI::mems()");
+    const size_type total = hit_offsets[count];
+    if(total == 0) { return; }
+    std::vector<uint32_t> begin(total), length(total); std::vector<uint64_t> sp(total), len(total);
+    gpuCheck(bwtm_mem_batch(ix, text.data(), offsets.data(), count, least, hit_offsets.data(), begin.data(), length.data(), sp.data(), len.data(), total), "FMI::mems()");
+    mems.resize(total);
+    for(size_type h = 0; h < total; h++) { mems[h].begin = begin[h]; mems[h].length = length[h]; mems[h].range = range_type(sp[h], sp[h] + len[h] - 1); }
+  }
+
   // The sequences with the ids [ids.first, ids.second] as comp values 1..5 in forward order, endmarkers not included: sequence k of the
   // range is text[offsets[k] .. offsets[k + 1]).  LF walks on the device (bwtm_sequences_extract: a sizing call, then the extracting one);
   // no sequence may be longer than max_len (0: 65536).  The index goes to the device if it is not there, and stays.

@@ -1,6 +1,6 @@
 /*
   kernels/quad.hip.h -- four lanes per LF walk: the record reader and the walk that the per-chain queries share (k_seq_*, k_locate*,
-  k_overlap_*), on the quad primitives of kernels/search_walk.hip.h (dpp_quad, quad_sum_u64, quad_or_u32, quad_rank_part; the layout of
+  k_overlap_*, k_ms_scan), on the quad primitives of kernels/search_walk.hip.h (dpp_quad, quad_sum_u64, quad_or_u32, quad_rank_part; the layout of
   a quad is described there).
   Part of bwtm_kernels.hip.h (included there, inside namespace bwtm, behind kernels/search_walk.hip.h); gfx950 only.
 */

@@ -219,6 +219,45 @@ int bwtm_find_edit_batch(const bwtm_index* index, const uint8_t* patterns, const
 /* What the calling thread's last bwtm_find_edit_batch did: stats[0] = nodes expanded (the sizes of all frontiers, every batch
    once), stats[1] = P and stats[2] = H of the formula above (the largest over the batches), stats[3] = levels run. */
 int bwtm_find_edit_stats(uint64_t stats[4]);
+/* Which pieces of a pattern occur at all, and how long they are: matching statistics and maximal exact matches (MEMs), the seeds of
+   seed-and-extend.  Patterns are laid out as for bwtm_find_batch: pattern k = patterns[offsets[k] .. offsets[k+1]), comp values 1..5
+   (N's comp value is a symbol like the others), at most 65 535 symbols each; no reverse complements.  "W occurs" means that
+   bwtm_find_batch returns a non-empty range for W: W lies inside a sequence, nothing spans an endmarker.
+   MATCHING STATISTICS of a pattern P of m symbols: for an end e in 1..m, l(e) is the largest l <= e such that P[e-l .. e) occurs, and 0
+   when P[e-1] alone does not.  The entry of symbol position i = e - 1 is (length, sp, count): length = l(e), and [sp, sp + count - 1]
+   is the closed range bwtm_find_batch returns for P[e-l .. e); (0, 0, 0) when l(e) = 0.  The entries of all patterns lie at index
+   offsets[k] + i - offsets[0], one per symbol of the text: each output holds offsets[count] - offsets[0] entries.  Any of the three
+   outputs may be NULL, not all.
+   A MAXIMAL EXACT MATCH of P is a pair (b, l) with l >= min_length >= 1 such that P[b .. b+l) occurs, b == 0 or P[b-1 .. b+l) does not
+   occur, and b + l == m or P[b .. b+l+1) does not occur: the substrings of P that occur and are contained in no longer substring of P
+   that occurs (BWA's super-maximal exact matches, stated on the pattern).  End e gives one iff l(e) >= min_length and (e == m or
+   l(e+1) <= l(e)); l(e+1) <= l(e) + 1 always holds.  A pattern has at most m MEMs; their begins and their ends both ascend strictly,
+   and they are reported in that order as (begin, length, sp, count), the range ready for bwtm_locate_ranges.  The empty pattern has
+   none.  The result is the same from run to run.
+   hit_offsets[count + 1] always receives the exclusive prefix sums of the MEMs per pattern.  capacity == 0, or all four output arrays
+   NULL: sizes only (the search still runs).  Otherwise capacity >= hit_offsets[count] (BWTM_EINVAL if not, and nothing is written)
+   and the MEMs of pattern k occupy [hit_offsets[k], hit_offsets[k + 1]) of out_begin / out_length / out_sp / out_count, any of which
+   may be NULL; nothing behind hit_offsets[count] is touched.
+   The statistics take one backward search per symbol of the text, four lanes each, which keeps its last range that is not empty.  The
+   MEMs take four lanes per pattern: its ends are searched from m downwards, an end gives a MEM iff its search gets below the begin of
+   the search before, and the pattern is finished when a search reaches its begin.  Both calls work in batches of bwtm_tune("mem_batch") patterns (default 2^20, at most 2^28, 0 restores the default),
+   cut at pattern boundaries; a batch also ends before its text reaches 2^29 symbols.  Device memory beyond the index, per batch of B
+   patterns with T symbols of text and M MEMs kept: at most 21 T + 8 B + 2^24 bytes (bwtm_matching_stats_batch) and
+   29 T + 28 M + 16 B + 2^25 bytes (bwtm_mem_batch) while every block stays below 512 MiB (api/mem.hip.h derives it).  A
+   bwtm_mem_batch call of several batches runs the search of each batch twice (once for the sizes, once before it emits).
+   Measured on an MI355X, 3.03 Gbase index, 2^16 patterns of 100 symbols cut from its reads, unchanged / 1 % / 5 % substituted
+   (tools/mem_bench.py): the statistics 160 / 151 / 111 ns per pattern, the MEMs at min_length 1
+   32.5 / 131.5 / 133.8 ns per pattern.  Not measured: longer patterns, patterns foreign to the index, calls of several batches.
+   Work on any whole index, not on a window.  BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument, a window of
+   an index, min_length == 0, offsets that decrease, a pattern longer than 65 535 symbols, a pattern symbol outside 1..5. */
+int bwtm_matching_stats_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
+                              uint32_t* out_lengths, uint64_t* out_sp, uint64_t* out_count);
+int bwtm_mem_batch(const bwtm_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t count, uint32_t min_length,
+                   uint64_t* hit_offsets /* count + 1 */, uint32_t* out_begin, uint32_t* out_length, uint64_t* out_sp,
+                   uint64_t* out_count, uint64_t capacity);
+/* What the calling thread's last call of either did: stats[0] = LF steps taken (pairs of ranks; every batch once), stats[1] = tasks
+   run (bwtm_matching_stats_batch: the symbols of the text, one search each; bwtm_mem_batch: the patterns), stats[2] = MEMs before min_length (0 after bwtm_matching_stats_batch), stats[3] = batches. */
+int bwtm_mem_stats(uint64_t stats[4]);
 /* Plain symbols [first, first + count) (BWT::extract, bwt.h:134-164), one byte each.  first <= bases and
    count <= bases - first, or BWTM_EINVAL (a sum that wraps included); first == bases with count == 0 is accepted. */
 int bwtm_extract(const bwtm_index* index, uint64_t first, uint64_t count, uint8_t* out);
