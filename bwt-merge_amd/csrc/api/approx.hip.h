@@ -1,6 +1,7 @@
 /*
   api/approx.hip.h -- patterns with up to d substitutions (bwtm_find_approx_batch): the backward search of a batch of patterns as one
-  frontier of ranges, level by level (kernels/approx.hip.h), its hits collected per pattern.  Part of bwtm_api.hip.
+  frontier of ranges, level by level (kernels/approx.hip.h), its hits collected per pattern.  Part of bwtm_api.hip.  Batches: see
+  api/batches.hip.h.
 
   Device memory of the call beyond the index, per batch of bwtm_tune("approx_batch") patterns, with P = the largest frontier of the batch
   (its first one has a root per pattern, so P >= patterns of the batch), H = the hits of the batch before max_hits and T = the bytes of its
@@ -25,7 +26,67 @@ namespace
 {
 // What the last call of this thread did: nodes expanded (the frontiers' sizes summed over the levels and batches), the largest frontier
 // of a batch, the most hits of a batch before max_hits, levels run.
-thread_local u64 t_approx_stats[4] = {0, 0, 0, 0};
+thread_local CallStats t_approx_stats;
+
+u64 pattern_batch_size() { return std::min<u64>((u64)g_tune.approx_batch, WALK_BATCH_LIMIT); }
+
+// Where a pattern search's hits go: the caller's arrays, any of them null.  cost = mismatches or edits; lengths only for the edit search.
+struct PatternHits
+{
+  u64* sp; u64* count; u8* cost; u32* lengths;
+  bool any() const { return sp || count || cost || lengths; }
+  PatternHits at(u64 i) const { return PatternHits{at_or_null(sp, i), at_or_null(count, i), at_or_null(cost, i), at_or_null(lengths, i)}; }
+};
+
+// What one batch of patterns is to this search and to that of api/edit.hip.h: its staged text and offsets, the hit stream (sp, count,
+// meta) of its levels, every pattern's slots in it, and the batch's hit offsets.
+struct PatternBatch : StagedTexts
+{
+  const bwtm_index* x = nullptr;
+  u32 max_cost = 0; u64 max_hits = 0;                   // the search's budget of mismatches or edits; hits kept per pattern (0: all)
+  DevBuf d_slots, d_base, d_out;
+  LevelTotals totals;
+  Frontier<3> hits;
+  u64 nhits = 0, kept_total = 0;
+
+  ApproxNodes hit_nodes(u64 capacity) const { return ApproxNodes{hits.array(0), hits.array(1), hits.array(2), std::min(capacity, hits.cap)}; }
+
+  // The patterns of offsets[0 .. nb] to the device, `slot_words` zeroed u64 for the marks, and an empty hit stream.
+  int stage(const u8* patterns, const u64* offsets, u64 nb, u64 slot_words)
+  {
+    nhits = 0;
+    TRY(StagedTexts::stage(patterns, offsets, nb));
+    TRY(d_slots.alloc(slot_words * sizeof(u64), true)); TRY(d_base.alloc((nb + 1) * sizeof(u64)));
+    return BWTM_OK;
+  }
+
+  // d_base[0 .. nb] holds the capped counts: hit_offsets[0 .. nb] = their scan, continuing `before`, the hits of the call's earlier batches.
+  int finish_offsets(const char* who, u64 nb, u64 before, u64* hit_offsets)
+  {
+    TRY(device_scan<0>(d_base.as<const u64>(), d_base.as<u64>(), nb + 1));
+    TRY(to_host(hit_offsets, d_base.as<const u64>(), nb + 1));
+    HIP_TRY(hipStreamSynchronize(CTX.stream));
+    kept_total = hit_offsets[nb];
+    if(kept_total > nhits) { return fail(BWTM_EINVAL, "%s: %llu hits kept of %llu found", who, (unsigned long long)kept_total, (unsigned long long)nhits); }
+    if(before != 0) { for(u64 k = 0; k <= nb; k++) { hit_offsets[k] += before; } }
+    return BWTM_OK;
+  }
+};
+
+// A call of a pattern search, over a Batch with search() and fill(): batches of pattern_batch_size() in the two rounds of api/batches.hip.h.
+// stats[0] counts the nodes expanded, once.
+template<class Batch>
+int pattern_run(const char* who, CallStats* stats, const bwtm_index* x, const u8* patterns, const u64* offsets, u64 count, u32 max_cost, u64 max_hits, u64* hit_offsets,
+                const PatternHits& out, u64 capacity)
+{
+  const u64 batch = std::min(pattern_batch_size(), count);
+  Batch b;
+  b.x = x; b.max_cost = max_cost; b.max_hits = max_hits;
+  return two_round_call(who, "hits", count, hit_offsets, out.any(), capacity, stats,
+    [&](u64 done) { return std::min(batch, count - done); },
+    [&](u64 done, u64 nb, u64* batch_offsets) { return b.search(patterns, offsets + done, nb, batch_offsets); },
+    [&](u64, u64 nb, u64 at) { return b.fill(nb, out.at(at)); });
+}
 
 ApproxNodes approx_nodes(const Frontier<3>& f, u64 capacity) { return ApproxNodes{f.array(0), f.array(1), f.array(2), std::min(capacity, f.cap)}; }
 
@@ -77,7 +138,7 @@ struct ApproxBatch : PatternBatch
     TRY(cur.reserve(nb, who));
     LAUNCH("approx_roots", k_approx_roots, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, d_off.as<const u64>(), nb, x->n, approx_nodes(cur, nb));
     u64 count = nb, peak = nb;
-    const u64 levels = std::max<u64>(longest, 1);                                               // an empty pattern's root becomes its hit in the first one
+    const u64 levels = std::max<u64>(longest(), 1);                                               // an empty pattern's root becomes its hit in the first one
     for(u64 t = 0; t < levels && count > 0; t++)
     {
       const u64 nblocks = div_up(count, block_nodes);
@@ -117,9 +178,7 @@ struct ApproxBatch : PatternBatch
     u64* o_sp = d_out.as<u64>(); u64* o_cnt = o_sp + kept_total; u8* o_mm = (u8*)(o_cnt + kept_total);
     LAUNCH("approx_gather", k_approx_gather, div_up(nhits, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.array(0), (const u64*)hits.array(1), (const u64*)hits.array(2), nhits, nb,
       (const u64*)first(), d_base.as<const u64>(), o_sp, o_cnt, o_mm, kept_total);
-    if(out.sp) { HIP_TRY(hipMemcpyAsync(out.sp, o_sp, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out.count) { HIP_TRY(hipMemcpyAsync(out.count, o_cnt, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out.cost) { HIP_TRY(hipMemcpyAsync(out.cost, o_mm, kept_total, hipMemcpyDeviceToHost, CTX.stream)); }
+    TRY(to_host(out.sp, o_sp, kept_total)); TRY(to_host(out.count, o_cnt, kept_total)); TRY(to_host(out.cost, o_mm, kept_total));
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers are reused
     return BWTM_OK;
   }
@@ -137,19 +196,14 @@ extern "C" int bwtm_find_approx_batch(const bwtm_index* x, const uint8_t* patter
   {
     return fail(BWTM_EINVAL, "bwtm_find_approx_batch: max_mismatches = %u is outside 0..%u", (unsigned)max_mismatches, (unsigned)APPROX_MAX_MISMATCHES);
   }
-  for(u32 j = 0; j < 4; j++) { t_approx_stats[j] = 0; }
+  t_approx_stats.reset();
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  TRY(validate_patterns("bwtm_find_approx_batch", patterns, offsets, count));
-  const int rc = pattern_run<ApproxBatch>("bwtm_find_approx_batch", t_approx_stats, x, patterns, offsets, count, max_mismatches, max_hits, hit_offsets,
+  TRY(validate_texts("bwtm_find_approx_batch", "pattern", patterns, offsets, count, APPROX_MAX_LEN));
+  const int rc = pattern_run<ApproxBatch>("bwtm_find_approx_batch", &t_approx_stats, x, patterns, offsets, count, max_mismatches, max_hits, hit_offsets,
     PatternHits{out_sp, out_count, out_mismatches, nullptr}, capacity);
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.stream); }                                 // the half-built state goes back to the pool behind this
   return rc;
 }
 
-extern "C" int bwtm_find_approx_stats(uint64_t stats[4])
-{
-  if(!stats) { return fail(BWTM_EINVAL, "bwtm_find_approx_stats: null argument"); }
-  for(u32 j = 0; j < 4; j++) { stats[j] = t_approx_stats[j]; }
-  return BWTM_OK;
-}
+extern "C" int bwtm_find_approx_stats(uint64_t stats[4]) { return t_approx_stats.get("bwtm_find_approx_stats", stats); }

@@ -25,7 +25,8 @@
   A block of 512 MiB or more is made of whole chunks of 1 GiB (api/context.hip.h): at that size add one chunk per block.
   bwtm_correct_sequences first takes the lengths of every batch into offsets of its own (8 (count + 1) bytes of host memory), so that max_len
   and the capacity are checked before anything is written: the caller's offsets, text, status and edit counts are untouched by a refused
-  call.  A call of one batch keeps those lengths, a call of several walks every batch a second time.
+  call.  A call of one batch keeps those lengths, a call of several walks every batch a second time.  Its second round runs whether or not
+  text is wanted, so it is not a two_round_call.  Batches: see api/batches.hip.h.
 */
 #pragma once
 
@@ -45,7 +46,7 @@ struct bwtm_corrector
 namespace
 {
 // What the last correct call of this thread did: table lookups, rounds run over all reads, the most edits in one read, batches.
-thread_local u64 t_correct_stats[4] = {0, 0, 0, 0};
+thread_local CallStats t_correct_stats;
 
 constexpr u64 CORRECT_MAX_ROUNDS = 65535;
 constexpr u64 CORRECT_LAUNCH_READS = 1ull << 25;        // a wave per read: 2^31 threads per launch
@@ -111,10 +112,8 @@ struct CorrectBatch
       LAUNCH("correct", k_correct_wave, div_up(part, CORRECT_WAVES), BLOCK_THREADS, c->table(), d_text, d_work.as<u8>(), d_off + first, part, max_rounds,
         d_status.as<u8>() + first, d_edits.as<u32>() + first, d_stats.as<unsigned long long>());
     }
-    if(out_text && bytes > 0) { HIP_TRY(hipMemcpyAsync(out_text, d_work.p, bytes, hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_status) { HIP_TRY(hipMemcpyAsync(out_status, d_status.p, nb, hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_edits) { HIP_TRY(hipMemcpyAsync(out_edits, d_edits.p, nb * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
-    HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers are reused
+    TRY(to_host(out_text, d_work.as<const u8>(), bytes)); TRY(to_host(out_status, d_status.as<const u8>(), nb)); TRY(to_host(out_edits, d_edits.as<const u32>(), nb));
+    HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers, and a staged batch's h_off, are reused
     t_correct_stats[3]++;
     return BWTM_OK;
   }
@@ -154,12 +153,7 @@ extern "C" uint64_t bwtm_corrector_solid(const bwtm_corrector* corrector) { retu
 extern "C" uint64_t bwtm_corrector_bytes(const bwtm_corrector* corrector) { return corrector ? corrector->codes.bytes + corrector->dir.bytes : 0; }
 extern "C" uint32_t bwtm_corrector_k(const bwtm_corrector* corrector) { return corrector ? corrector->k : 0; }
 
-extern "C" int bwtm_correct_stats(uint64_t stats[4])
-{
-  if(!stats) { return fail(BWTM_EINVAL, "bwtm_correct_stats: null argument"); }
-  for(u32 j = 0; j < 4; j++) { stats[j] = t_correct_stats[j]; }
-  return BWTM_OK;
-}
+extern "C" int bwtm_correct_stats(uint64_t stats[4]) { return t_correct_stats.get("bwtm_correct_stats", stats); }
 
 extern "C" int bwtm_correct_batch(const bwtm_corrector* corrector, const uint8_t* patterns, const uint64_t* offsets, uint64_t count, uint32_t max_rounds,
                                   uint8_t* out_text, uint8_t* out_status, uint32_t* out_edits)
@@ -167,41 +161,19 @@ extern "C" int bwtm_correct_batch(const bwtm_corrector* corrector, const uint8_t
   if(!corrector || (count > 0 && !offsets)) { return fail(BWTM_EINVAL, "bwtm_correct_batch: null argument"); }
   ENTER(corrector->ctx);
   if(max_rounds > CORRECT_MAX_ROUNDS) { return fail(BWTM_EINVAL, "bwtm_correct_batch: max_rounds = %u is above 65535", (unsigned)max_rounds); }
-  for(u32 j = 0; j < 4; j++) { t_correct_stats[j] = 0; }
+  t_correct_stats.reset();
   if(count == 0) { return BWTM_OK; }
-  for(u64 k = 0; k < count; k++)
-  {
-    if(offsets[k] > offsets[k + 1]) { return fail(BWTM_EINVAL, "bwtm_correct_batch: offsets must not decrease (pattern %llu)", (unsigned long long)k); }
-  }
-  if(offsets[count] > offsets[0] && !patterns) { return fail(BWTM_EINVAL, "bwtm_correct_batch: null pattern text"); }
-  for(u64 k = 0; k < count; k++)
-  {
-    for(u64 p = offsets[k]; p < offsets[k + 1]; p++)
-    {
-      if(patterns[p] < 1 || patterns[p] > 5)
-      {
-        return fail(BWTM_EINVAL, "bwtm_correct_batch: pattern %llu holds the symbol %u at offset %llu (comp values 1..5)", (unsigned long long)k, (unsigned)patterns[p],
-          (unsigned long long)(p - offsets[k]));
-      }
-    }
-  }
+  TRY(validate_texts("bwtm_correct_batch", "pattern", patterns, offsets, count, 0));
   const u64 batch = std::min(correct_batch_size(), count);
   CorrectBatch b;
   b.c = corrector; b.max_rounds = max_rounds;
   TRY(b.alloc(batch));
-  DevBuf d_text, d_off;
-  std::vector<u64> h_off;
+  StagedTexts t;
   for(u64 done = 0; done < count; done += batch)
   {
     const u64 nb = std::min(batch, count - done);
-    const u64 base = offsets[done], bytes = offsets[done + nb] - base;
-    h_off.resize(nb + 1);
-    for(u64 k = 0; k <= nb; k++) { h_off[k] = offsets[done + k] - base; }
-    TRY(d_text.alloc(bytes)); TRY(d_off.alloc((nb + 1) * sizeof(u64)));
-    if(bytes > 0) { HIP_TRY(hipMemcpyAsync(d_text.p, patterns + base, bytes, hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (nb + 1) * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    TRY(b.run(d_text.as<const u8>(), d_off.as<const u64>(), nb, bytes, (out_text ? out_text + base : nullptr), (out_status ? out_status + done : nullptr),
-      (out_edits ? out_edits + done : nullptr)));                                                // awaits the stream: h_off is reused
+    TRY(t.stage(patterns, offsets + done, nb));
+    TRY(b.run(t.d_text.as<const u8>(), t.d_off.as<const u64>(), nb, t.bytes, at_or_null(out_text, offsets[done]), at_or_null(out_status, done), at_or_null(out_edits, done)));
   }
   return b.finish();
 }
@@ -218,7 +190,7 @@ extern "C" int bwtm_correct_sequences(const bwtm_corrector* corrector, const bwt
   ENTER(corrector->ctx);
   if(max_rounds > CORRECT_MAX_ROUNDS) { return fail(BWTM_EINVAL, "bwtm_correct_sequences: max_rounds = %u is above 65535", (unsigned)max_rounds); }
   TRY(check_max_len(who, &max_len));
-  for(u32 j = 0; j < 4; j++) { t_correct_stats[j] = 0; }
+  t_correct_stats.reset();
   if(count == 0) { if(offsets) { offsets[0] = 0; } return BWTM_OK; }
   TRY(check_sequence_ids(who, x, ids, first_id, count));
   std::vector<u64> own(count + 1, 0);                                                           // the caller's offsets are written after the last check
@@ -232,18 +204,9 @@ extern "C" int bwtm_correct_sequences(const bwtm_corrector* corrector, const bwt
   // lengths -> batch-local offsets in s.d_off; fill: they continue the caller's offsets behind offsets[done]
   auto sizes = [&](u64 done, u64 nb, bool fill) -> int
   {
-    u64 bad = 0;
-    TRY(s.lengths(x, (ids ? ids + done : nullptr), first_id + done, nb, max_len, &bad));
-    if(bad != SEQ_STATUS_NONE)
-    {
-      bad += done;
-      return fail(BWTM_EINVAL, "bwtm_correct_sequences: sequence %llu is longer than max_len = %llu (or the index is damaged)",
-        (unsigned long long)(ids ? ids[bad] : first_id + bad), (unsigned long long)max_len);
-    }
-    LAUNCH("overlap_widen", k_overlap_widen, div_up(nb + 1, BLOCK_THREADS), BLOCK_THREADS, s.d_len.as<const u32>(), nb, s.d_off.as<u64>());
-    TRY(device_scan<0>(s.d_off.as<const u64>(), s.d_off.as<u64>(), nb + 1));
+    TRY(s.offsets_on_device(who, "max_len", x, at_or_null(ids, done), first_id + done, nb, max_len));
     if(!fill) { return BWTM_OK; }
-    HIP_TRY(hipMemcpyAsync(h_off.data(), s.d_off.p, (nb + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+    TRY(to_host(h_off.data(), s.d_off.as<const u64>(), nb + 1));
     HIP_TRY(hipStreamSynchronize(CTX.stream));
     for(u64 k = 1; k <= nb; k++) { offsets[done + k] = offsets[done] + h_off[k]; }
     return BWTM_OK;
@@ -261,9 +224,8 @@ extern "C" int bwtm_correct_sequences(const bwtm_corrector* corrector, const bwt
     const u64 nb = std::min(batch, count - done);
     if(!single) { TRY(sizes(done, nb, false)); }
     const u64 local = offsets[done + nb] - offsets[done];
-    TRY(s.emit(x, (ids ? ids + done : nullptr), first_id + done, nb, local));                   // the text at its exact size
-    TRY(b.run(s.d_text.as<const u8>(), s.d_off.as<const u64>(), nb, local, (want_text ? text + offsets[done] : nullptr), (out_status ? out_status + done : nullptr),
-      (out_edits ? out_edits + done : nullptr)));
+    TRY(s.emit(x, at_or_null(ids, done), first_id + done, nb, local));                          // the text at its exact size
+    TRY(b.run(s.d_text.as<const u8>(), s.d_off.as<const u64>(), nb, local, (want_text ? text + offsets[done] : nullptr), at_or_null(out_status, done), at_or_null(out_edits, done)));
   }
   return b.finish();
 }

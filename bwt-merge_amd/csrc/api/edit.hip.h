@@ -1,7 +1,7 @@
 /*
   api/edit.hip.h -- patterns within edit distance e (bwtm_find_edit_batch): the backward search of a batch of patterns as one frontier of
   ranges whose nodes carry a band of the edit-distance matrix, level by level (kernels/edit.hip.h), its hits collected per pattern and
-  length.  Part of bwtm_api.hip, behind api/approx.hip.h, whose hit stream it shares.
+  length.  Part of bwtm_api.hip, behind api/approx.hip.h, whose hit stream it shares.  Batches: see api/batches.hip.h.
 
   Device memory of the call beyond the index, per batch of bwtm_tune("approx_batch") patterns, with P = the largest frontier of the batch
   (its first one has a root per pattern, so P >= patterns of the batch), H = the hits of the batch before max_hits, T = the bytes of its
@@ -27,7 +27,7 @@ namespace
 {
 // What the last call of this thread did: nodes expanded (the frontiers' sizes summed over the levels and batches), the largest frontier
 // of a batch, the most hits of a batch before max_hits, levels run.
-thread_local u64 t_edit_stats[4] = {0, 0, 0, 0};
+thread_local CallStats t_edit_stats;
 
 EditNodes edit_nodes(const Frontier<4>& f, u64 capacity) { return EditNodes{f.array(0), f.array(1), f.array(2), f.array(3), std::min(capacity, f.cap)}; }
 
@@ -51,7 +51,7 @@ struct EditBatch : PatternBatch
     TRY(cur.reserve(nb, who));
     LAUNCH("edit_roots", k_edit_roots, div_up(nb, BLOCK_THREADS), BLOCK_THREADS, d_off.as<const u64>(), nb, x->n, edit_nodes(cur, nb));
     u64 count = nb, peak = nb;
-    const u64 levels = std::max<u64>(longest + max_cost, 1);                                    // a root that is a hit becomes one in the first level
+    const u64 levels = std::max<u64>(longest() + max_cost, 1);                                    // a root that is a hit becomes one in the first level
     for(u64 t = 0; t < levels && count > 0; t++)
     {
       const u64 nblocks = div_up(count, BLOCK_THREADS);
@@ -98,10 +98,8 @@ struct EditBatch : PatternBatch
     u64* o_sp = d_out.as<u64>(); u64* o_cnt = o_sp + kept_total; u32* o_len = (u32*)(o_cnt + kept_total); u8* o_ed = (u8*)(o_len + kept_total);
     LAUNCH("edit_gather", k_edit_gather, div_up(nhits, BLOCK_THREADS), BLOCK_THREADS, (const u64*)hits.array(0), (const u64*)hits.array(1), (const u64*)hits.array(2), nhits,
       d_off.as<const u64>(), nb, max_cost, (const u64*)first(), (const u64*)end(nb), d_base.as<const u64>(), o_sp, o_cnt, o_len, o_ed, kept_total);
-    if(out.sp) { HIP_TRY(hipMemcpyAsync(out.sp, o_sp, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out.count) { HIP_TRY(hipMemcpyAsync(out.count, o_cnt, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out.lengths) { HIP_TRY(hipMemcpyAsync(out.lengths, o_len, kept_total * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out.cost) { HIP_TRY(hipMemcpyAsync(out.cost, o_ed, kept_total, hipMemcpyDeviceToHost, CTX.stream)); }
+    TRY(to_host(out.sp, o_sp, kept_total)); TRY(to_host(out.count, o_cnt, kept_total));
+    TRY(to_host(out.lengths, o_len, kept_total)); TRY(to_host(out.cost, o_ed, kept_total));
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers are reused
     return BWTM_OK;
   }
@@ -119,19 +117,14 @@ extern "C" int bwtm_find_edit_batch(const bwtm_index* x, const uint8_t* patterns
   {
     return fail(BWTM_EINVAL, "bwtm_find_edit_batch: max_edits = %u is outside 0..%u", (unsigned)max_edits, (unsigned)EDIT_MAX_EDITS);
   }
-  for(u32 j = 0; j < 4; j++) { t_edit_stats[j] = 0; }
+  t_edit_stats.reset();
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  TRY(validate_patterns("bwtm_find_edit_batch", patterns, offsets, count));
-  const int rc = pattern_run<EditBatch>("bwtm_find_edit_batch", t_edit_stats, x, patterns, offsets, count, max_edits, max_hits, hit_offsets,
+  TRY(validate_texts("bwtm_find_edit_batch", "pattern", patterns, offsets, count, APPROX_MAX_LEN));
+  const int rc = pattern_run<EditBatch>("bwtm_find_edit_batch", &t_edit_stats, x, patterns, offsets, count, max_edits, max_hits, hit_offsets,
     PatternHits{out_sp, out_count, out_edits, out_lengths}, capacity);
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.stream); }                                 // the half-built state goes back to the pool behind this
   return rc;
 }
 
-extern "C" int bwtm_find_edit_stats(uint64_t stats[4])
-{
-  if(!stats) { return fail(BWTM_EINVAL, "bwtm_find_edit_stats: null argument"); }
-  for(u32 j = 0; j < 4; j++) { stats[j] = t_edit_stats[j]; }
-  return BWTM_OK;
-}
+extern "C" int bwtm_find_edit_stats(uint64_t stats[4]) { return t_edit_stats.get("bwtm_find_edit_stats", stats); }

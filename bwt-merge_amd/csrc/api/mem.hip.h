@@ -19,8 +19,7 @@
      2^24 / 2^25  what the pool rounds up: a block of 1 MiB or more to 64 KiB, of 64 MiB or more to 2 MiB, a smaller one to 256 bytes.
   A block of 512 MiB or more is made of whole chunks of 1 GiB (api/context.hip.h): at that size add one chunk per block.
 
-  A call of one batch keeps the batch's arrays between the sizes and the filling; a call of several batches runs the search of each
-  batch twice, as overlap_run does (the arrays of all batches do not stay anywhere: the memory is that of one batch).
+  Batches: see api/batches.hip.h.
 */
 #pragma once
 
@@ -28,7 +27,7 @@ namespace
 {
 // What the last call of this thread (either of the two) did: LF steps taken (rank pairs), tasks run (symbols for the statistics, patterns
 // for the MEMs), MEMs before min_length, batches.
-thread_local u64 t_mem_stats[4] = {0, 0, 0, 0};
+thread_local CallStats t_mem_stats;
 
 // A batch of the statistics is one launch of four lanes per symbol, and a grid holds fewer than 2^32 threads: a batch (of either call)
 // also ends before its text reaches 2^29 symbols (a pattern has fewer than 2^16, so every batch holds a pattern).
@@ -43,36 +42,29 @@ u64 mem_batch_patterns(const u64* offsets, u64 done, u64 count)
   return std::max<u64>((u64)(cut - (offsets + done)) - 1, 1);
 }
 
-// One batch of patterns: its text and offsets on the device, the matching statistics, and for the MEMs the flags, slots and hit offsets.
-struct MemBatch
+// One batch of patterns: its staged text and offsets, the matching statistics, and for the MEMs the flags, slots and hit offsets.
+struct MemBatch : StagedTexts
 {
   const bwtm_index* x = nullptr;
   u32 min_length = 1;
-  DevBuf d_text, d_off, d_len, d_sp, d_cnt, d_flags, d_per, d_counters, d_out;
-  std::vector<u64> h_off;
-  u64 total = 0, kept_total = 0;                        // of the staged batch: its symbols, its MEMs kept
+  DevBuf d_len, d_sp, d_cnt, d_flags, d_per, d_counters, d_out;
+  u64 kept_total = 0;                                   // of the staged batch: its MEMs kept
 
   // The patterns of offsets[0 .. nb] to the device, and the two zeroed counters (steps, MEMs of any length).
   int stage(const u8* patterns, const u64* offsets, u64 nb)
   {
-    const u64 base = offsets[0];
-    total = offsets[nb] - base;
-    h_off.resize(nb + 1);
-    for(u64 k = 0; k <= nb; k++) { h_off[k] = offsets[k] - base; }
-    TRY(d_text.alloc(total)); TRY(d_off.alloc((nb + 1) * sizeof(u64))); TRY(d_counters.alloc(2 * sizeof(u64), true));
-    if(total > 0) { HIP_TRY(hipMemcpyAsync(d_text.p, patterns + base, total, hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (nb + 1) * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    return BWTM_OK;
+    TRY(d_counters.alloc(2 * sizeof(u64), true));                                               // zeroed on the stream before the copies, as it always was
+    return StagedTexts::stage(patterns, offsets, nb);
   }
   unsigned long long* counter(u32 j) const { return d_counters.as<unsigned long long>() + j; }
 
   // The matching statistics of the staged batch into the arrays asked for.
   int stats_scan(u64 nb, bool want_len, bool want_sp, bool want_cnt)
   {
-    if(want_len) { TRY(d_len.alloc(total * sizeof(u32))); }
-    if(want_sp) { TRY(d_sp.alloc(total * sizeof(u64))); }
-    if(want_cnt) { TRY(d_cnt.alloc(total * sizeof(u64))); }
-    LAUNCH("ms_scan", k_ms_scan, div_up(4 * total, BLOCK_THREADS), BLOCK_THREADS, x->view(), d_text.as<const u8>(), d_off.as<const u64>(), nb, total,
+    if(want_len) { TRY(d_len.alloc(bytes * sizeof(u32))); }
+    if(want_sp) { TRY(d_sp.alloc(bytes * sizeof(u64))); }
+    if(want_cnt) { TRY(d_cnt.alloc(bytes * sizeof(u64))); }
+    LAUNCH("ms_scan", k_ms_scan, div_up(4 * bytes, BLOCK_THREADS), BLOCK_THREADS, x->view(), d_text.as<const u8>(), d_off.as<const u64>(), nb, bytes,
       (want_len ? d_len.as<u32>() : nullptr), (want_sp ? d_sp.as<u64>() : nullptr), (want_cnt ? d_cnt.as<u64>() : nullptr), counter(0));
     return BWTM_OK;
   }
@@ -84,43 +76,43 @@ struct MemBatch
     TRY(stage(patterns, offsets, nb));
     kept_total = 0;
     t_mem_stats[3]++;
-    if(total == 0)
+    if(bytes == 0)
     {
       HIP_TRY(hipStreamSynchronize(CTX.stream));                                                // h_off is reused
       for(u64 k = 1; k <= nb; k++) { hit_offsets[k] = before; }
       return BWTM_OK;
     }
-    TRY(d_flags.alloc((total + 1) * sizeof(u64)));
+    TRY(d_flags.alloc((bytes + 1) * sizeof(u64)));
     u64 tasks = nb;
 #ifdef BWTM_DIAGNOSTICS
     if(g_tune.mem_kernel == 1)                                                                  // the A/B partner: one quad per end, then the rule on the lengths
     {
       TRY(d_per.alloc((nb + 1) * sizeof(u64), true));
       TRY(stats_scan(nb, true, true, true));
-      LAUNCH("mem_flag", k_mem_flag, div_up(total + 1, BLOCK_THREADS), BLOCK_THREADS, d_len.as<const u32>(), d_off.as<const u64>(), nb, total, min_length,
+      LAUNCH("mem_flag", k_mem_flag, div_up(bytes + 1, BLOCK_THREADS), BLOCK_THREADS, d_len.as<const u32>(), d_off.as<const u64>(), nb, bytes, min_length,
         d_flags.as<u64>(), d_per.as<u64>(), counter(1));
-      tasks = total;
+      tasks = bytes;
     }
     else
 #endif
     {
-      TRY(d_len.alloc(total * sizeof(u32))); TRY(d_sp.alloc(total * sizeof(u64))); TRY(d_cnt.alloc(total * sizeof(u64)));
+      TRY(d_len.alloc(bytes * sizeof(u32))); TRY(d_sp.alloc(bytes * sizeof(u64))); TRY(d_cnt.alloc(bytes * sizeof(u64)));
       TRY(d_per.alloc((nb + 1) * sizeof(u64)));
-      LAUNCH("mem_pattern", k_mem_pattern, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), d_text.as<const u8>(), d_off.as<const u64>(), nb, total, min_length,
+      LAUNCH("mem_pattern", k_mem_pattern, div_up(4 * nb, BLOCK_THREADS), BLOCK_THREADS, x->view(), d_text.as<const u8>(), d_off.as<const u64>(), nb, bytes, min_length,
         d_len.as<u32>(), d_sp.as<u64>(), d_cnt.as<u64>(), d_flags.as<u64>(), d_per.as<u64>(), counter(0), counter(1));
     }
-    TRY(device_scan<0>(d_flags.as<const u64>(), d_flags.as<u64>(), total + 1));
+    TRY(device_scan<0>(d_flags.as<const u64>(), d_flags.as<u64>(), bytes + 1));
     TRY(device_scan<0>(d_per.as<const u64>(), d_per.as<u64>(), nb + 1));
-    TRY(fetch_u64(d_flags.as<u64>() + total, 0));
+    TRY(fetch_u64(d_flags.as<u64>() + bytes, 0));
     TRY(fetch_u64(d_counters.as<u64>(), 1, 2));
-    HIP_TRY(hipMemcpyAsync(hit_offsets, d_per.p, (nb + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+    TRY(to_host(hit_offsets, d_per.as<const u64>(), nb + 1));
     HIP_TRY(hipStreamSynchronize(CTX.stream));
     kept_total = hit_offsets[nb];
     t_mem_stats[0] += CTX.host_scratch[1]; t_mem_stats[1] += tasks; t_mem_stats[2] += CTX.host_scratch[2];
-    if(kept_total != CTX.host_scratch[0] || kept_total > total)
+    if(kept_total != CTX.host_scratch[0] || kept_total > bytes)
     {
       return fail(BWTM_EINVAL, "%s: %llu MEMs counted per pattern, %llu flagged, of %llu symbols", who, (unsigned long long)kept_total, (unsigned long long)CTX.host_scratch[0],
-        (unsigned long long)total);
+        (unsigned long long)bytes);
     }
     if(before != 0) { for(u64 k = 0; k <= nb; k++) { hit_offsets[k] += before; } }              // a later batch of the call
     return BWTM_OK;
@@ -132,45 +124,47 @@ struct MemBatch
     if(kept_total == 0) { return BWTM_OK; }
     TRY(d_out.alloc(28 * kept_total));
     u64* o_sp = d_out.as<u64>(); u64* o_cnt = o_sp + kept_total; u32* o_begin = (u32*)(o_cnt + kept_total); u32* o_len = o_begin + kept_total;
-    LAUNCH("mem_emit", k_mem_emit, div_up(total, BLOCK_THREADS), BLOCK_THREADS, d_len.as<const u32>(), d_sp.as<const u64>(), d_cnt.as<const u64>(), d_off.as<const u64>(), nb, total,
+    LAUNCH("mem_emit", k_mem_emit, div_up(bytes, BLOCK_THREADS), BLOCK_THREADS, d_len.as<const u32>(), d_sp.as<const u64>(), d_cnt.as<const u64>(), d_off.as<const u64>(), nb, bytes,
       d_flags.as<const u64>(), kept_total, (out_begin ? o_begin : nullptr), (out_length ? o_len : nullptr), (out_sp ? o_sp : nullptr), (out_count ? o_cnt : nullptr));
-    if(out_begin) { HIP_TRY(hipMemcpyAsync(out_begin, o_begin, kept_total * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_length) { HIP_TRY(hipMemcpyAsync(out_length, o_len, kept_total * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_sp) { HIP_TRY(hipMemcpyAsync(out_sp, o_sp, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
-    if(out_count) { HIP_TRY(hipMemcpyAsync(out_count, o_cnt, kept_total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream)); }
+    TRY(to_host(out_begin, o_begin, kept_total)); TRY(to_host(out_length, o_len, kept_total)); TRY(to_host(out_sp, o_sp, kept_total)); TRY(to_host(out_count, o_cnt, kept_total));
     HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers are reused
     return BWTM_OK;
   }
 };
 
-// First every batch is searched, so that hit_offsets is complete and the capacity is checked before anything else is written; then the
-// MEMs are emitted.  A call of one batch keeps its arrays between the two; a call of several searches every batch a second time.
+// The batches of a bwtm_mem_batch call in the two rounds of api/batches.hip.h.
 int mem_run(const char* who, const bwtm_index* x, const u8* patterns, const u64* offsets, u64 count, u32 min_length, u64* hit_offsets,
             u32* out_begin, u32* out_length, u64* out_sp, u64* out_count, u64 capacity)
 {
-  const bool single = (mem_batch_patterns(offsets, 0, count) == count);
   MemBatch b;
   b.x = x; b.min_length = min_length;
+  return two_round_call(who, "MEMs", count, hit_offsets, out_begin || out_length || out_sp || out_count, capacity, &t_mem_stats,
+    [&](u64 done) { return mem_batch_patterns(offsets, done, count); },
+    [&](u64 done, u64 nb, u64* batch_offsets) { return b.search(who, patterns, offsets + done, nb, batch_offsets); },
+    [&](u64, u64 nb, u64 at) { return b.fill(nb, at_or_null(out_begin, at), at_or_null(out_length, at), at_or_null(out_sp, at), at_or_null(out_count, at)); });
+}
+
+// Every batch of a bwtm_matching_stats_batch call: staged, scanned, and the arrays asked for brought to the caller at the batch's first symbol.
+int matching_stats_run(const bwtm_index* x, const u8* patterns, const u64* offsets, u64 count, u32* out_lengths, u64* out_sp, u64* out_count)
+{
+  MemBatch b;
+  b.x = x;
   for(u64 done = 0, nb = 0; done < count; done += nb)
   {
     nb = mem_batch_patterns(offsets, done, count);
-    TRY(b.search(who, patterns, offsets + done, nb, hit_offsets + done));
-  }
-  const u64 total = hit_offsets[count];
-  if(!(out_begin || out_length || out_sp || out_count) || capacity == 0 || total == 0) { return BWTM_OK; }   // sizes only
-  if(capacity < total) { return fail(BWTM_EINVAL, "%s: capacity %llu is too small (%llu MEMs)", who, (unsigned long long)capacity, (unsigned long long)total); }
-  u64 kept[4];
-  for(u32 j = 0; j < 4; j++) { kept[j] = t_mem_stats[j]; }
-  for(u64 done = 0, nb = 0; done < count; done += nb)
-  {
-    nb = mem_batch_patterns(offsets, done, count);
-    const u64 at = hit_offsets[done];
-    if(!single)
+    const u64 at = offsets[done] - offsets[0];
+    TRY(b.stage(patterns, offsets + done, nb));
+    t_mem_stats[3]++;
+    if(b.bytes > 0)
     {
-      TRY(b.search(who, patterns, offsets + done, nb, hit_offsets + done));
-      for(u32 j = 0; j < 4; j++) { t_mem_stats[j] = kept[j]; }                                   // the same work a second time
+      TRY(b.stats_scan(nb, out_lengths != nullptr, out_sp != nullptr, out_count != nullptr));
+      TRY(fetch_u64(b.d_counters.as<u64>(), 0));
+      TRY(to_host(at_or_null(out_lengths, at), b.d_len.as<const u32>(), b.bytes));
+      TRY(to_host(at_or_null(out_sp, at), b.d_sp.as<const u64>(), b.bytes));
+      TRY(to_host(at_or_null(out_count, at), b.d_cnt.as<const u64>(), b.bytes));
     }
-    TRY(b.fill(nb, (out_begin ? out_begin + at : nullptr), (out_length ? out_length + at : nullptr), (out_sp ? out_sp + at : nullptr), (out_count ? out_count + at : nullptr)));
+    HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // the batch's buffers and h_off are reused
+    if(b.bytes > 0) { t_mem_stats[0] += CTX.host_scratch[0]; t_mem_stats[1] += b.bytes; }
   }
   return BWTM_OK;
 }
@@ -180,36 +174,13 @@ int mem_run(const char* who, const bwtm_index* x, const u8* patterns, const u64*
 extern "C" int bwtm_matching_stats_batch(const bwtm_index* x, const uint8_t* patterns, const uint64_t* offsets, uint64_t count,
                                          uint32_t* out_lengths, uint64_t* out_sp, uint64_t* out_count)
 {
-  const char* const who = "bwtm_matching_stats_batch";
   if(!x || (count > 0 && !offsets) || !(out_lengths || out_sp || out_count)) { return fail(BWTM_EINVAL, "bwtm_matching_stats_batch: null argument"); }
   WHOLE_INDEX(x, "bwtm_matching_stats_batch");
   ENTER(x->ctx);
-  for(u32 j = 0; j < 4; j++) { t_mem_stats[j] = 0; }
+  t_mem_stats.reset();
   if(count == 0) { return BWTM_OK; }
-  TRY(validate_patterns(who, patterns, offsets, count));
-  MemBatch b;
-  b.x = x;
-  int rc = BWTM_OK;
-  for(u64 done = 0, nb = 0; done < count && rc == BWTM_OK; done += nb)
-  {
-    nb = mem_batch_patterns(offsets, done, count);
-    const u64 at = offsets[done] - offsets[0];
-    rc = b.stage(patterns, offsets + done, nb);
-    t_mem_stats[3]++;
-    if(rc == BWTM_OK && b.total > 0) { rc = b.stats_scan(nb, out_lengths != nullptr, out_sp != nullptr, out_count != nullptr); }
-    if(rc != BWTM_OK) { break; }
-    hipError_t e = hipSuccess;
-    if(b.total > 0)
-    {
-      e = hipMemcpyAsync(CTX.host_scratch, b.d_counters.p, sizeof(u64), hipMemcpyDeviceToHost, CTX.stream);
-      if(e == hipSuccess && out_lengths) { e = hipMemcpyAsync(out_lengths + at, b.d_len.p, b.total * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream); }
-      if(e == hipSuccess && out_sp) { e = hipMemcpyAsync(out_sp + at, b.d_sp.p, b.total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream); }
-      if(e == hipSuccess && out_count) { e = hipMemcpyAsync(out_count + at, b.d_cnt.p, b.total * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream); }
-    }
-    if(e == hipSuccess) { e = hipStreamSynchronize(CTX.stream); }                                // the batch's buffers are reused
-    if(e != hipSuccess) { rc = fail(BWTM_ENODEV, "bwtm_matching_stats_batch: %s", hipGetErrorString(e)); break; }
-    if(b.total > 0) { t_mem_stats[0] += CTX.host_scratch[0]; t_mem_stats[1] += b.total; }
-  }
+  TRY(validate_texts("bwtm_matching_stats_batch", "pattern", patterns, offsets, count, APPROX_MAX_LEN));
+  const int rc = matching_stats_run(x, patterns, offsets, count, out_lengths, out_sp, out_count);
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.stream); }                                 // the half-built state goes back to the pool behind this
   return rc;
 }
@@ -221,18 +192,13 @@ extern "C" int bwtm_mem_batch(const bwtm_index* x, const uint8_t* patterns, cons
   WHOLE_INDEX(x, "bwtm_mem_batch");
   ENTER(x->ctx);
   if(min_length == 0) { return fail(BWTM_EINVAL, "bwtm_mem_batch: min_length must be at least 1"); }
-  for(u32 j = 0; j < 4; j++) { t_mem_stats[j] = 0; }
+  t_mem_stats.reset();
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  TRY(validate_patterns("bwtm_mem_batch", patterns, offsets, count));
+  TRY(validate_texts("bwtm_mem_batch", "pattern", patterns, offsets, count, APPROX_MAX_LEN));
   const int rc = mem_run("bwtm_mem_batch", x, patterns, offsets, count, min_length, hit_offsets, out_begin, out_length, out_sp, out_count, capacity);
   if(rc != BWTM_OK) { (void)hipStreamSynchronize(CTX.stream); }                                 // the half-built state goes back to the pool behind this
   return rc;
 }
 
-extern "C" int bwtm_mem_stats(uint64_t stats[4])
-{
-  if(!stats) { return fail(BWTM_EINVAL, "bwtm_mem_stats: null argument"); }
-  for(u32 j = 0; j < 4; j++) { stats[j] = t_mem_stats[j]; }
-  return BWTM_OK;
-}
+extern "C" int bwtm_mem_stats(uint64_t stats[4]) { return t_mem_stats.get("bwtm_mem_stats", stats); }

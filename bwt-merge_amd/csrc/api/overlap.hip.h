@@ -1,6 +1,7 @@
 /*
   api/overlap.hip.h -- suffix-prefix overlaps of a batch of queries against the collection (bwtm_overlap_batch, bwtm_overlap_sequences):
   one backward search per query, its rank(., 0) pairs looked up in the locator's table (kernels/overlap.hip.h).  Part of bwtm_api.hip.
+  Batches: see api/batches.hip.h.
 */
 #pragma once
 
@@ -62,7 +63,7 @@ struct OverlapBatch
     TRY(device_scan<0>(d_rbase.as<const u64>(), d_rbase.as<u64>(), nb + 1));
     TRY(device_scan<0>(d_hbase.as<const u64>(), d_hbase.as<u64>(), nb + 1));
     TRY(fetch_u64(d_rbase.as<u64>() + nb, 1));
-    HIP_TRY(hipMemcpyAsync(hit_offsets, d_hbase.p, (nb + 1) * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+    TRY(to_host(hit_offsets, d_hbase.as<const u64>(), nb + 1));
     HIP_TRY(hipStreamSynchronize(CTX.stream));
     nrecs = CTX.host_scratch[1]; kept_total = hit_offsets[nb];
     if(before != 0) { for(u64 k = 0; k <= nb; k++) { hit_offsets[k] += before; } }              // a later batch of the call
@@ -87,8 +88,7 @@ struct OverlapBatch
       u64 slot = 0;
       TRY(status.read(&slot));
       if(slot != SEQ_STATUS_NONE) { *bad = done + slot; return BWTM_OK; }                         // nothing of a failed batch reaches the caller
-      HIP_TRY(hipMemcpyAsync(out_ids + done, d_ids.p, nh * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
-      HIP_TRY(hipMemcpyAsync(out_lengths + done, d_len.p, nh * sizeof(u64), hipMemcpyDeviceToHost, CTX.stream));
+      TRY(to_host(out_ids + done, d_ids.as<const u64>(), nh)); TRY(to_host(out_lengths + done, d_len.as<const u64>(), nh));
       HIP_TRY(hipStreamSynchronize(CTX.stream));                                                // the batch's buffers are reused
     }
     return BWTM_OK;
@@ -96,45 +96,33 @@ struct OverlapBatch
 };
 
 // Both calls: prepare(done, nb, &d_text, &d_off) puts the text and the nb + 1 batch-local offsets of the queries done .. done + nb - 1 on
-// the device.  First every batch is counted, so that hit_offsets is complete and the capacity is checked before anything else is written;
-// then every batch is emitted and expanded.  A call of one batch keeps its text and counts between the two; a call of several prepares
-// and counts every batch a second time (the counts of all batches do not stay anywhere: the memory is that of one batch).
+// the device.  Batches of overlap_batch_size() in the two rounds of api/batches.hip.h: counted, then emitted and expanded.
 template<class Prepare>
 int overlap_run(const char* who, const bwtm_locator* loc, u64 count, u64 min_overlap, u64 max_hits, u64* hit_offsets, u64* out_ids, u64* out_lengths,
                 u64 capacity, Prepare&& prepare)
 {
   const u64 batch = std::min(overlap_batch_size(), count);
-  const bool single = (batch >= count);
   OverlapBatch b;
   b.loc = loc; b.min_overlap = min_overlap; b.max_hits = max_hits;
   TRY(b.alloc(batch));
   const u8* d_text = nullptr; const u64* d_off = nullptr;
-  for(u64 done = 0; done < count; done += batch)
+  auto size = [&](u64 done, u64 nb, u64* batch_offsets) -> int
   {
-    const u64 nb = std::min(batch, count - done);
     TRY(prepare(done, nb, &d_text, &d_off));
-    TRY(b.count(d_text, d_off, nb, hit_offsets + done));
-  }
-  const u64 total = hit_offsets[count];
-  if(!out_ids || capacity == 0 || total == 0) { return BWTM_OK; }                               // sizes only
-  if(!out_lengths) { return fail(BWTM_EINVAL, "%s: null argument", who); }
-  if(capacity < total) { return fail(BWTM_EINVAL, "%s: capacity %llu is too small (%llu hits)", who, (unsigned long long)capacity, (unsigned long long)total); }
-  for(u64 done = 0; done < count; done += batch)
+    TRY(b.count(d_text, d_off, nb, batch_offsets));
+    // A call that will fill needs both arrays, and says so before the capacity is looked at.  "Will fill" is two_round_call's own condition
+    // for going past "sizes only" (an array wanted, a capacity, something found), known here with the last batch's count: the two change together.
+    if(done + nb == count && out_ids && capacity > 0 && batch_offsets[nb] > 0 && !out_lengths) { return fail(BWTM_EINVAL, "%s: null argument", who); }
+    return BWTM_OK;
+  };
+  auto fill = [&](u64, u64 nb, u64 at) -> int
   {
-    const u64 nb = std::min(batch, count - done);
-    if(!single)
-    {
-      TRY(prepare(done, nb, &d_text, &d_off));
-      TRY(b.count(d_text, d_off, nb, hit_offsets + done));
-    }
     u64 bad = 0;
-    TRY(b.expand(d_text, d_off, nb, out_ids + hit_offsets[done], out_lengths + hit_offsets[done], &bad));
-    if(bad != SEQ_STATUS_NONE)
-    {
-      return fail(BWTM_EINVAL, "%s: hit %llu has no sequence in the locator's table (the index or the table is damaged)", who, (unsigned long long)(hit_offsets[done] + bad));
-    }
-  }
-  return BWTM_OK;
+    TRY(b.expand(d_text, d_off, nb, out_ids + at, out_lengths + at, &bad));
+    if(bad == SEQ_STATUS_NONE) { return BWTM_OK; }
+    return fail(BWTM_EINVAL, "%s: hit %llu has no sequence in the locator's table (the index or the table is damaged)", who, (unsigned long long)(at + bad));
+  };
+  return two_round_call(who, "hits", count, hit_offsets, out_ids != nullptr, capacity, nullptr, [&](u64 done) { return std::min(batch, count - done); }, size, fill);
 }
 
 } // namespace
@@ -147,34 +135,12 @@ extern "C" int bwtm_overlap_batch(const bwtm_locator* loc, const uint8_t* querie
   if(min_overlap == 0) { return fail(BWTM_EINVAL, "bwtm_overlap_batch: min_overlap must be at least 1"); }
   hit_offsets[0] = 0;
   if(count == 0) { return BWTM_OK; }
-  for(u64 k = 0; k < count; k++)
-  {
-    if(offsets[k] > offsets[k + 1]) { return fail(BWTM_EINVAL, "bwtm_overlap_batch: offsets must not decrease (query %llu)", (unsigned long long)k); }
-  }
-  if(offsets[count] > offsets[0] && !queries) { return fail(BWTM_EINVAL, "bwtm_overlap_batch: null query text"); }
-  for(u64 k = 0; k < count; k++)
-  {
-    for(u64 p = offsets[k]; p < offsets[k + 1]; p++)
-    {
-      if(queries[p] < 1 || queries[p] > 5)
-      {
-        return fail(BWTM_EINVAL, "bwtm_overlap_batch: query %llu holds the symbol %u at offset %llu (comp values 1..5)", (unsigned long long)k, (unsigned)queries[p],
-          (unsigned long long)(p - offsets[k]));
-      }
-    }
-  }
-  DevBuf d_text, d_off;
-  std::vector<u64> h_off;
+  TRY(validate_texts("bwtm_overlap_batch", "query", queries, offsets, count, 0));
+  StagedTexts t;
   auto prepare = [&](u64 done, u64 nb, const u8** text_out, const u64** off_out) -> int
   {
-    const u64 base = offsets[done], bytes = offsets[done + nb] - base;
-    h_off.resize(nb + 1);
-    for(u64 k = 0; k <= nb; k++) { h_off[k] = offsets[done + k] - base; }
-    TRY(d_text.alloc(bytes)); TRY(d_off.alloc((nb + 1) * sizeof(u64)));
-    if(bytes > 0) { HIP_TRY(hipMemcpyAsync(d_text.p, queries + base, bytes, hipMemcpyHostToDevice, CTX.stream)); }
-    HIP_TRY(hipMemcpyAsync(d_off.p, h_off.data(), (nb + 1) * sizeof(u64), hipMemcpyHostToDevice, CTX.stream));
-    HIP_TRY(hipStreamSynchronize(CTX.stream));                                                  // h_off is reused
-    *text_out = d_text.as<const u8>(); *off_out = d_off.as<const u64>();
+    TRY(t.stage(queries, offsets + done, nb));
+    *text_out = t.d_text.as<const u8>(); *off_out = t.d_off.as<const u64>();
     return BWTM_OK;
   };
   return overlap_run("bwtm_overlap_batch", loc, count, min_overlap, max_hits, hit_offsets, out_ids, out_lengths, capacity, prepare);
@@ -195,19 +161,10 @@ extern "C" int bwtm_overlap_sequences(const bwtm_locator* loc, const uint64_t* i
   TRY(s.alloc(std::min(overlap_batch_size(), count), ids != nullptr, true, false));           // lengths and offsets stay on the device
   auto prepare = [&](u64 done, u64 nb, const u8** text_out, const u64** off_out) -> int
   {
-    u64 bad = 0;
-    TRY(s.lengths(x, (ids ? ids + done : nullptr), first_id + done, nb, loc->max_len, &bad));
-    if(bad != SEQ_STATUS_NONE)
-    {
-      bad += done;
-      return fail(BWTM_EINVAL, "bwtm_overlap_sequences: sequence %llu is longer than the locator's max_len = %llu (or the index is damaged)",
-        (unsigned long long)(ids ? ids[bad] : first_id + bad), (unsigned long long)loc->max_len);
-    }
-    LAUNCH("overlap_widen", k_overlap_widen, div_up(nb + 1, BLOCK_THREADS), BLOCK_THREADS, s.d_len.as<const u32>(), nb, s.d_off.as<u64>());
-    TRY(device_scan<0>(s.d_off.as<const u64>(), s.d_off.as<u64>(), nb + 1));
+    TRY(s.offsets_on_device("bwtm_overlap_sequences", "the locator's max_len", x, at_or_null(ids, done), first_id + done, nb, loc->max_len));
     TRY(fetch_u64(s.d_off.as<u64>() + nb, 1));
     HIP_TRY(hipStreamSynchronize(CTX.stream));
-    TRY(s.emit(x, (ids ? ids + done : nullptr), first_id + done, nb, CTX.host_scratch[1]));    // the text at its exact size
+    TRY(s.emit(x, at_or_null(ids, done), first_id + done, nb, CTX.host_scratch[1]));      // the text at its exact size
     *text_out = s.d_text.as<const u8>(); *off_out = s.d_off.as<const u64>();
     return BWTM_OK;
   };

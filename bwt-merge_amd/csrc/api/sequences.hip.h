@@ -61,8 +61,8 @@ int check_sequence_ids(const char* who, const bwtm_index* x, const u64* ids, u64
   return BWTM_OK;
 }
 
-// The per-batch stage of reading sequences by id, shared by bwtm_sequences_extract (which brings the text to the host) and
-// bwtm_overlap_sequences (which searches it where it is): the device buffers of one batch and its two launches.
+// The per-batch stage of reading sequences by id, shared by bwtm_sequences_extract (which brings the text to the host),
+// bwtm_overlap_sequences and bwtm_correct_sequences (which work on it where it is): the device buffers of one batch and its two launches.
 struct SeqBatch
 {
   DevBuf d_ids, d_len, d_off, d_text;
@@ -90,6 +90,21 @@ struct SeqBatch
       d_len.as<u32>(), status.word());
     if(on_host) { HIP_TRY(hipMemcpyAsync(h_len.data(), d_len.p, nb * sizeof(u32), hipMemcpyDeviceToHost, CTX.stream)); }
     return status.read(bad);
+  }
+  // For a batch whose lengths stay on the device (!on_host): lengths(), refused in the name of `who` if a sequence is longer than max_len
+  // (`limit` is what the message calls it), then the nb + 1 batch-local offsets into d_off: the lengths widened and scanned.  ids and
+  // first_id are those of the batch's first sequence.
+  int offsets_on_device(const char* who, const char* limit, const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 max_len)
+  {
+    u64 bad = 0;
+    TRY(lengths(x, ids, first_id, nb, max_len, &bad));
+    if(bad != SEQ_STATUS_NONE)
+    {
+      return fail(BWTM_EINVAL, "%s: sequence %llu is longer than %s = %llu (or the index is damaged)", who, (unsigned long long)(ids ? ids[bad] : first_id + bad), limit,
+        (unsigned long long)max_len);
+    }
+    LAUNCH("overlap_widen", k_overlap_widen, div_up(nb + 1, BLOCK_THREADS), BLOCK_THREADS, d_len.as<const u32>(), nb, d_off.as<u64>());
+    return device_scan<0>(d_off.as<const u64>(), d_off.as<u64>(), nb + 1);
   }
   // the batch's text allocated at its exact size `local`, h_off up (on_host), k_seq_emit (not launched for an empty text); nothing is awaited
   int emit(const bwtm_index* x, const u64* ids, u64 first_id, u64 nb, u64 local)

@@ -15,18 +15,21 @@
     api/group.hip.h     the parts of a multi-GPU merge: shared control block (barrier, small all-gathers), exported arenas (raw pointer / HIP IPC)
     api/pmerge.hip.h    the merge over PARTITIONED records, one part per GPU: windows from byte shares, cuts, the routed search, the second half
     api/sequences.hip.h sequences by id: lengths, offsets and text in batches of bounded device memory
+    api/batches.hip.h   the batch scheme of the calls that take texts from the host, stated once for the files marked (b): the texts' validation, a
+                        staged batch, the two rounds of a call that sizes before it fills, optional arrays to the host, a call's statistics
     api/locate.hip.h    positions to (sequence id, offset): the locator's table, positions and ranges located in batches
-    api/overlap.hip.h   suffix-prefix overlaps: one backward search per query, counted, then emitted and expanded through the locator's table
+    api/overlap.hip.h   suffix-prefix overlaps: one backward search per query, counted, then emitted and expanded through the locator's table (b)
     api/frontier.hip.h  the host side of the level scheme the next four share: the doubling frontier of parallel arrays, a level's totals with their
-                        scan and read-back, a batch of patterns with its hit stream and offsets, the two rounds of a pattern call
+                        scan and read-back
     api/kmers.hip.h     the distinct k-mers of an index with counts and ranges: the trie's levels on two ping-pong frontiers, the spectrum
     api/kmer_join.hip.h the k-mers of two indexes with their counts and insertion points in each: one joint walk, the summary of the result
-    api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern
-    api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length
+    api/approx.hip.h    patterns with up to d substitutions: a batch's backward search as one frontier of ranges, the hits gathered per pattern (b); a batch of
+                        patterns with its hit stream and offsets, which the next shares
+    api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length (b)
     api/correct.hip.h   k-mer error correction of reads: the solid k-mers of a spectrum as a sorted table with a bucket directory, a wave per read,
-                        on patterns from the host or on sequences extracted on the device, in batches of bounded device memory
+                        on patterns from the host or on sequences extracted on the device, in batches of bounded device memory (b)
     api/mem.hip.h       matching statistics and maximal exact matches of patterns: one backward search per symbol of a batch's text; for the MEMs a quad
-                        per pattern that flags the ends that give one, two scans and one emit, in batches of bounded device memory
+                        per pattern that flags the ends that give one, two scans and one emit, in batches of bounded device memory (b)
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
     api/partition.hip.h the first, host-driven form of the partitioned search (same build only; kept for its tests and A/B measurements)
 */
@@ -66,6 +69,7 @@ using namespace bwtm;
 #endif
 #include "api/ingest.hip.h"
 #include "api/sequences.hip.h"
+#include "api/batches.hip.h"
 #include "api/locate.hip.h"
 #include "api/overlap.hip.h"
 #include "api/frontier.hip.h"

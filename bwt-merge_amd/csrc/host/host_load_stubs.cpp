@@ -1,6 +1,6 @@
 /*
-  The C ABI as host_load_test links it: the functions that program's link asks for and the locator's entry points (fmi.h), none of which does anything.  There is
-  no device behind them: whatever would allocate, upload or download answers BWTM_ENODEV, sizes are 0, handles nullptr.  With
+  The C ABI as host_load_test and host_cpu_test_san link it: the functions those programs' links ask for and the locator's entry points (fmi.h), none of which does
+  anything.  There is no device behind them: whatever would allocate, upload or download answers BWTM_ENODEV, sizes are 0, handles nullptr.  With
   bwtm_host_alloc failing, HostArray falls back to malloc (support.h).
 */
 #include <bwtm.h>

@@ -304,6 +304,10 @@ def test_argument_errors_name_the_offender(gpu, oracle, genome):
     offsets = np.array([0, 40, 30, 120], dtype=np.uint64)
     args = (text.ctypes.data_as(capi.p_u8), offsets.ctypes.data_as(capi.p_u64), 3, 10, None, st.ctypes.data_as(capi.p_u8), None)
     assert lib.bwtm_correct_batch(cor.h, *args) != 0 and "offsets must not decrease (pattern 1)" in lib.bwtm_last_error().decode()
+    spoiled = text.copy(); spoiled[0] = 0                                         # two faults: the offsets are looked at before any text is read through them
+    later = np.array([0, 40, 90, 80], dtype=np.uint64)
+    assert lib.bwtm_correct_batch(cor.h, spoiled.ctypes.data_as(capi.p_u8), later.ctypes.data_as(capi.p_u64), *args[2:]) != 0
+    assert "offsets must not decrease (pattern 2)" in lib.bwtm_last_error().decode()
     assert lib.bwtm_correct_batch(None, *args) != 0 and "null argument" in lib.bwtm_last_error().decode()
     assert lib.bwtm_correct_batch(cor.h, args[0], None, *args[2:]) != 0 and "null argument" in lib.bwtm_last_error().decode()
     offsets[2] = 80
@@ -332,7 +336,8 @@ def test_argument_errors_name_the_offender(gpu, oracle, genome):
     b0, b1, fp, before_counts = gpu.window_blocks(host(gpu, f), 1000, 5000)
     Cs = (C.c_uint64 * 7)(*[int(v) for v in f.C])
     out = capi.vp()
-    capi.check(lib.bwtm_index_upload_window(f.data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before_counts, int(f.bases), int(f.sequences), Cs, 0, C.byref(out)))
+    data = f.data                                        # a copy of the native bytes, alive over the call
+    capi.check(lib.bwtm_index_upload_window(data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before_counts, int(f.bases), int(f.sequences), Cs, 0, C.byref(out)))
     W = gpu.Index(out)
     with pytest.raises(gpu.BwtmError) as e:
         cor.correct_sequences(W, first=0, count=1, text=False)

@@ -32,6 +32,14 @@ def test_facade_logic_without_gpu(bwtm):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_facade_logic_under_sanitizers(bwtm):
+    """CPU check: the same program under AddressSanitizer and UBSan, linked against the stub ABI (`make host_cpu_test_san`): the facade's
+    codecs and the plain C++ of the library's batch scheme (validate_texts, two_round_call) read and write nothing they should not."""
+    subprocess.check_call(["make", "-C", HOST, "-s", "host_cpu_test_san"])
+    out = subprocess.run([os.path.join(HOST, "host_cpu_test_san")], capture_output=True, text=True)
+    assert out.returncode == 0 and "Sanitizer" not in out.stderr and "runtime error:" not in out.stderr, out.stdout + out.stderr
+
+
 def write_plain(path, fmi):
     CHARS[fmi.symbols].tofile(path)
 

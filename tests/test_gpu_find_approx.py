@@ -194,6 +194,43 @@ def test_batches_give_the_same_result(gpu, indexes):
     same(indexes["genome"].find_approx(patterns, 2), want)
 
 
+def batched_patterns():
+    """33 patterns for approx_batch = 7, five batches: seven mixed ones; the seven empty ones, which every position matches (a hit each, and
+    nothing else: the batch has no text); seven mixed; seven 41-mers, longer than any read (no hit: the batch contributes nothing); five mixed."""
+    mixed = [p for p in mixed_patterns("genome") if 0 < len(p) < 41]
+    none = cut_patterns(collection("genome").rows, (41,), 7, 51)
+    return mixed[:7] + [np.zeros(0, dtype=np.uint8)] * 7 + mixed[7:14] + none + mixed[14:19]
+
+
+def test_the_two_rounds_of_a_call_of_many_batches(gpu, indexes):
+    """approx_batch = 7, so that the call searches every batch twice: the sizing call, a capacity one short, the exact capacity; the
+    statistics of the filling call are those of the sizing call; a batch of empty patterns and a batch without hits in the middle."""
+    x, coll, patterns = indexes["genome"], collection("genome"), batched_patterns()
+    want = expected(coll, patterns, 2)
+    per = np.diff(want[0].astype(np.int64))
+    total = int(want[0][-1])
+    assert len(patterns) == 33 and per[7:14].tolist() == [1] * 7 and not per[21:28].any() and per[:7].sum() > 7 and per[28:].sum() > 5
+    assert np.all(want[0][21:29] == want[0][21])                                  # flat across the fourth batch
+    try:
+        gpu.tune("approx_batch", 7)
+        rc, ho, sp, cnt, mm = raw(gpu, x, patterns, 2, 0, 0, total + 3)
+        sized = gpu.find_approx_stats()
+        assert rc == 0 and np.array_equal(ho, want[0]) and np.all(sp == GUARD64) and np.all(cnt == GUARD64) and np.all(mm == GUARD8)
+        rc, ho, sp, cnt, mm = raw(gpu, x, patterns, 2, 0, total - 1, total + 3)
+        assert rc == 1 and "bwtm_find_approx_batch: capacity %d is too small (%d hits)" % (total - 1, total) in last_error(gpu)
+        assert np.array_equal(ho, want[0]) and np.all(sp == GUARD64) and np.all(cnt == GUARD64) and np.all(mm == GUARD8)
+        rc, ho, sp, cnt, mm = raw(gpu, x, patterns, 2, 0, total, total + 3)
+        filled = gpu.find_approx_stats()
+    finally:
+        gpu.tune("approx_batch", 0)
+    assert rc == 0
+    same((ho, sp[:total], cnt[:total], mm[:total]), want)
+    assert np.all(sp[total:] == GUARD64) and np.all(cnt[total:] == GUARD64) and np.all(mm[total:] == GUARD8)
+    assert filled == sized and sized["expanded"] > len(patterns) and sized["frontier_peak"] >= 7      # the second round leaves no trace
+    h = int(want[0][7])
+    assert sp[h: h + 7].tolist() == [0] * 7 and cnt[h: h + 7].tolist() == [x.bases] * 7 and not mm[h: h + 7].any()
+
+
 def test_max_hits_sizes_capacity_and_null_arrays(gpu, indexes):
     x, coll, patterns = indexes["iid"], collection("iid"), mixed_patterns("iid")
     full = mixed_expected("iid", 2)
@@ -258,6 +295,8 @@ def test_argument_errors(gpu, oracle, indexes):
     refused("pattern 2 holds the symbol 6 at offset 0", patterns=[ones(3), ones(0), np.array([6], dtype=np.uint8)])
     refused("offsets must not decrease (pattern 1)", text_offsets=(ones(8), np.array([0, 3, 2, 8], dtype=np.uint64)))
     refused("pattern 1 has 65536 symbols", patterns=[ones(2), ones(65536)])
+    # two faults: the offsets are looked at before any text is read through them
+    refused("offsets must not decrease (pattern 2)", text_offsets=(np.array([0, 2, 3, 4, 1, 1, 2, 3], dtype=np.uint8), np.array([0, 3, 5, 4], dtype=np.uint64)))
     assert gpu.capi.lib().bwtm_find_approx_batch(None, None, None, 0, 0, 0, None, None, None, None, 0) != 0 and "null argument" in last_error(gpu)
     # the longest pattern that is accepted, and the index still answers
     hit_offsets, sp, count, mm = x.find_approx([ones(65535)], 0)

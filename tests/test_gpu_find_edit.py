@@ -206,6 +206,45 @@ def test_batches_give_the_same_result(gpu, indexes):
     same(indexes["genome"].find_edit(patterns, 2), want)
 
 
+def batched_patterns():
+    """33 patterns for approx_batch = 7, five batches: seven mixed ones; the seven empty ones, which the empty string and every single symbol
+    are within one edit of (the batch has no text); seven mixed; seven random 20-mers that nothing in the reads is near (no hit: the batch
+    contributes nothing); five mixed."""
+    mixed = [p for p in mixed_patterns("genome") if 0 < len(p) <= 12]
+    none = [np.random.default_rng(70 + j).integers(1, 5, size=20).astype(np.uint8) for j in range(7)]
+    return mixed[:7] + [np.zeros(0, dtype=np.uint8)] * 7 + mixed[7:14] + none + mixed[14:19]
+
+
+def test_the_two_rounds_of_a_call_of_many_batches(gpu, indexes):
+    """approx_batch = 7, so that the call searches every batch twice: the sizing call, a capacity one short, the exact capacity; the
+    statistics of the filling call are those of the sizing call; a batch of empty patterns and a batch without hits in the middle."""
+    x, coll, patterns = indexes["genome"], collection("genome"), batched_patterns()
+    want = expected(coll, patterns, 1)
+    per = np.diff(want[0].astype(np.int64))
+    total = int(want[0][-1])
+    assert len(patterns) == 33 and len(set(per[7:14].tolist())) == 1 and per[7] >= 2 and not per[21:28].any() and per[:7].sum() > 7 and per[28:].sum() > 5
+    assert np.all(want[0][21:29] == want[0][21])                                  # flat across the fourth batch
+    untouched = lambda arrays: all(np.all(a == g) for a, g in zip(arrays, GUARDS))
+    try:
+        gpu.tune("approx_batch", 7)
+        rc, ho, *arrays = raw(gpu, x, patterns, 1, 0, 0, total + 3)
+        sized = gpu.find_edit_stats()
+        assert rc == 0 and np.array_equal(ho, want[0]) and untouched(arrays)
+        rc, ho, *arrays = raw(gpu, x, patterns, 1, 0, total - 1, total + 3)
+        assert rc == 1 and "bwtm_find_edit_batch: capacity %d is too small (%d hits)" % (total - 1, total) in last_error(gpu)
+        assert np.array_equal(ho, want[0]) and untouched(arrays)
+        rc, ho, *arrays = raw(gpu, x, patterns, 1, 0, total, total + 3)
+        filled = gpu.find_edit_stats()
+    finally:
+        gpu.tune("approx_batch", 0)
+    assert rc == 0
+    same((ho,) + tuple(a[:total] for a in arrays), want)
+    assert untouched([a[total:] for a in arrays])
+    assert filled == sized and sized["expanded"] > len(patterns) and sized["frontier_peak"] >= 7      # the second round leaves no trace
+    h = int(want[0][7])
+    assert (int(arrays[0][h]), int(arrays[1][h]), int(arrays[2][h]), int(arrays[3][h])) == (0, x.bases, 0, 0)    # the empty string first
+
+
 def test_max_hits_sizes_capacity_and_null_arrays(gpu, indexes):
     x, coll, patterns = indexes["iid"], collection("iid"), mixed_patterns("iid")
     full = mixed_expected("iid", 2)
@@ -270,6 +309,8 @@ def test_argument_errors(gpu, oracle, indexes):
     refused("pattern 2 holds the symbol 6 at offset 0", patterns=[ones(3), ones(0), np.array([6], dtype=np.uint8)])
     refused("offsets must not decrease (pattern 1)", text_offsets=(ones(8), np.array([0, 3, 2, 8], dtype=np.uint64)))
     refused("pattern 1 has 65536 symbols", patterns=[ones(2), ones(65536)])
+    # two faults: the offsets are looked at before any text is read through them
+    refused("offsets must not decrease (pattern 2)", text_offsets=(np.array([0, 2, 3, 4, 1, 1, 2, 3], dtype=np.uint8), np.array([0, 3, 5, 4], dtype=np.uint64)))
     assert gpu.capi.lib().bwtm_find_edit_batch(None, None, None, 0, 0, 0, None, None, None, None, None, 0) != 0 and "null argument" in last_error(gpu)
     # the longest pattern that is accepted, and the index still answers
     got = x.find_edit([ones(65535)], 0)

@@ -336,7 +336,8 @@ def test_argument_errors(gpu, oracle, genome):
     b0, b1, fp, before_counts = gpu.window_blocks(ha, 1000, 5000)
     Cs = (C.c_uint64 * 7)(*[int(v) for v in fa.C])
     out = vp()
-    gpu.capi.check(lib.bwtm_index_upload_window(fa.data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before_counts, int(fa.bases), int(fa.sequences), Cs, 0, C.byref(out)))
+    data = fa.data                                        # a copy of the native bytes, alive over the call
+    gpu.capi.check(lib.bwtm_index_upload_window(data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before_counts, int(fa.bases), int(fa.sequences), Cs, 0, C.byref(out)))
     W = gpu.Index(out)
     for x, y, side in ((W, B, "a is a window"), (A, W, "b is a window"), (W, W, "a is a window")):
         with pytest.raises(gpu.BwtmError) as e:

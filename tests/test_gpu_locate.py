@@ -222,7 +222,8 @@ def test_every_form_of_an_index(gpu, oracle):
     b0, b1, fp, before = gpu.window_blocks(ha, 1000, 5000)
     Cs = (C.c_uint64 * 7)(*[int(v) for v in fa.C])
     out = gpu.capi.vp()
-    gpu.capi.check(gpu.capi.lib().bwtm_index_upload_window(fa.data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before, int(fa.bases), int(fa.sequences), Cs, 0, C.byref(out)))
+    data = fa.data                                        # a copy of the native bytes, alive over the call
+    gpu.capi.check(gpu.capi.lib().bwtm_index_upload_window(data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before, int(fa.bases), int(fa.sequences), Cs, 0, C.byref(out)))
     W = gpu.Index(out)
     with pytest.raises(gpu.BwtmError) as e:
         W.locator()

@@ -183,6 +183,44 @@ def test_capacity_and_null_outputs(gpu, three_hundred):
     assert x.mems([])[0].tolist() == [0] and x.mems([(), ()])[0].tolist() == [0, 0, 0] and x.matching_stats([()])[0].size == 0
 
 
+def test_the_two_rounds_of_a_call_of_many_batches(gpu, three_hundred):
+    """mem_batch = 7, so that the call searches every batch twice: the sizing call, a capacity one short, the exact capacity; the
+    statistics of the filling call are those of the sizing call; a batch of seven empty patterns in the middle contributes nothing."""
+    x, rows, brute = three_hundred
+    lib, p_u64, p_u32 = gpu.capi.lib(), gpu.capi.p_u64, gpu.capi.p_u32
+    reads = [r for r in rows if len(r) > 0]
+    patterns = varied_patterns(rows, 32)[:14] + [()] * 7 + reads[:12]
+    want = expected_mems(brute, patterns, 3)
+    per = np.diff(want[0].astype(np.int64))
+    total = int(want[0][-1])
+    assert len(patterns) == 33 and not per[14:21].any() and per[:14].sum() > 14 and per[21:].sum() > 5
+    assert np.all(want[0][14:22] == want[0][14])                                  # flat across the third batch
+    text, offsets, tp, op = pack(gpu, patterns)
+
+    def call(capacity):
+        hit_offsets = np.full(len(patterns) + 1, FILL, dtype=np.uint64)
+        outs = [np.full(total + 3, FILL32, dtype=np.uint32), np.full(total + 3, FILL32, dtype=np.uint32), np.full(total + 3, FILL, dtype=np.uint64), np.full(total + 3, FILL, dtype=np.uint64)]
+        rc = lib.bwtm_mem_batch(x.h, tp, op, len(patterns), 3, hit_offsets.ctypes.data_as(p_u64), outs[0].ctypes.data_as(p_u32), outs[1].ctypes.data_as(p_u32),
+                                outs[2].ctypes.data_as(p_u64), outs[3].ctypes.data_as(p_u64), capacity)
+        return rc, hit_offsets, outs
+
+    untouched = lambda outs: all(np.all(o == (FILL32 if o.dtype == np.uint32 else FILL)) for o in outs)
+    try:
+        gpu.tune("mem_batch", 7)
+        rc, ho, outs = call(0)
+        sized = gpu.mem_stats()
+        assert rc == 0 and np.array_equal(ho, want[0]) and untouched(outs)
+        rc, ho, outs = call(total - 1)
+        assert rc == 1 and "bwtm_mem_batch: capacity %d is too small (%d MEMs)" % (total - 1, total) in lib.bwtm_last_error().decode()
+        assert np.array_equal(ho, want[0]) and untouched(outs)
+        rc, ho, outs = call(total)
+        filled = gpu.mem_stats()
+    finally:
+        gpu.tune("mem_batch", 0)
+    assert rc == 0 and same((ho,) + tuple(o[:total] for o in outs), want) and untouched([o[total:] for o in outs])
+    assert filled == sized and sized["batches"] == 5 and sized["tasks"] == len(patterns) - 7 and sized["steps"] > 0 and sized["mems"] >= total    # a batch without text runs no task; the second round leaves no trace
+
+
 def test_every_einval_names_its_offender(gpu, oracle, three_hundred):
     x, rows, brute = three_hundred
     lib, p_u64, p_u32, p_u8 = gpu.capi.lib(), gpu.capi.p_u64, gpu.capi.p_u32, gpu.capi.p_u8
@@ -207,6 +245,8 @@ def test_every_einval_names_its_offender(gpu, oracle, three_hundred):
         assert rc == 1 and name in msg and "pattern 0 holds the symbol 6 at offset 2" in msg, msg
         rc, msg = call([1, 2, 3, 4, 1, 1, 2, 3], [0, 5, 3, 8])
         assert rc == 1 and name in msg and "offsets must not decrease (pattern 1)" in msg, msg
+        rc, msg = call([0, 2, 3, 4, 1, 1, 2, 3], [0, 3, 5, 4])                   # two faults: the offsets are looked at before any text is read through them
+        assert rc == 1 and name in msg and "offsets must not decrease (pattern 2)" in msg, msg
         rc, msg = call(np.ones(65536 + 3, dtype=np.uint8), [0, 3, 65536 + 3])
         assert rc == 1 and name in msg and "pattern 1 has 65536 symbols" in msg, msg
         rc, msg = call([1, 2, 3], [0, 3], index=None)

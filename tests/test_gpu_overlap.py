@@ -173,6 +173,42 @@ def test_batches_give_the_same_result(gpu, oracle):
     x.free()
 
 
+def test_the_two_rounds_of_a_call_of_many_batches(gpu, three_hundred):
+    """overlap_batch = 64, so that bwtm_overlap_batch counts every batch twice: the sizing call, a capacity one short, the exact capacity;
+    a batch of sixty-four queries shorter than min_overlap in the middle contributes nothing."""
+    x, loc, rows, table = three_hundred
+    lib, p_u64, p_u8 = gpu.capi.lib(), gpu.capi.p_u64, gpu.capi.p_u8
+    short = [tuple(r[-(TAU - 1):]) for r in rows if len(r) >= TAU][:64]
+    queries = rows[:64] + short + rows[64:164]
+    want = expected(table, queries, TAU)
+    per = np.diff(want[0].astype(np.int64))
+    total = int(want[0][-1])
+    assert len(short) == 64 and len(queries) == 228 and not per[64:128].any() and per[:64].sum() > 64 and per[128:].sum() > 100
+    assert np.all(want[0][64:129] == want[0][64])                                 # flat across the second batch
+    offsets = np.zeros(len(queries) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(q) for q in queries])
+    text = np.ascontiguousarray(np.concatenate([np.asarray(q, dtype=np.uint8) for q in queries]))
+
+    def call(capacity):
+        hit_offsets = np.full(len(queries) + 1, FILL, dtype=np.uint64)
+        ids, lens = np.full(total + 3, FILL, dtype=np.uint64), np.full(total + 3, FILL, dtype=np.uint64)
+        rc = lib.bwtm_overlap_batch(loc.h, text.ctypes.data_as(p_u8), offsets.ctypes.data_as(p_u64), len(queries), TAU, 0, hit_offsets.ctypes.data_as(p_u64),
+                                    ids.ctypes.data_as(p_u64), lens.ctypes.data_as(p_u64), capacity)
+        return rc, hit_offsets, ids, lens
+
+    try:
+        gpu.tune("overlap_batch", 64)
+        rc, ho, ids, lens = call(0)
+        assert rc == 0 and np.array_equal(ho, want[0]) and np.all(ids == FILL) and np.all(lens == FILL)
+        rc, ho, ids, lens = call(total - 1)
+        assert rc == 1 and "bwtm_overlap_batch: capacity %d is too small (%d hits)" % (total - 1, total) in lib.bwtm_last_error().decode()
+        assert np.array_equal(ho, want[0]) and np.all(ids == FILL) and np.all(lens == FILL)
+        rc, ho, ids, lens = call(total)
+    finally:
+        gpu.tune("overlap_batch", 0)
+    assert rc == 0 and same((ho, ids[:total], lens[:total]), want) and np.all(ids[total:] == FILL) and np.all(lens[total:] == FILL)
+
+
 def test_every_form_of_an_index(gpu, oracle):
     """An uploaded native stream, the result of a merge (ids >= a.sequences are b's reads; a read planted in both sides overlaps across
     them), a builder's result (records only)."""
@@ -292,6 +328,8 @@ def test_errors_without_hangs(gpu, oracle):
     assert rc == 1 and "query 0 holds the symbol 6 at offset 2" in msg, msg
     rc, msg = batch_rc([1, 2, 3, 4, 1, 1, 2, 3], [0, 5, 3, 8])
     assert rc == 1 and "offsets must not decrease (query 1)" in msg, msg
+    rc, msg = batch_rc([0, 2, 3, 4, 1, 1, 2, 3], [0, 3, 5, 4])                   # two faults: the offsets are looked at before any text is read through them
+    assert rc == 1 and "offsets must not decrease (query 2)" in msg, msg
     with pytest.raises(gpu.BwtmError) as e:
         loc.overlaps(ids=[3, 300, 4], min_overlap=TAU)
     assert "sequence 300 out of range (300 sequences)" in str(e.value)

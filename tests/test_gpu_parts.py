@@ -199,7 +199,8 @@ def test_part_errors_reach_every_part(gpu, oracle):
     b0, b1, fp, before = gpu.window_blocks(ha, 1000, 50000)
     import ctypes as C
     Cs = (C.c_uint64 * 7)(*[int(v) for v in a.C])
-    gpu.capi.check(gpu.capi.lib().bwtm_index_upload_window(a.data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before, int(a.bases), int(a.sequences), Cs, 0, C.byref(out)))
+    data = a.data                                         # a copy of the native bytes, alive over the call
+    gpu.capi.check(gpu.capi.lib().bwtm_index_upload_window(data.ctypes.data + 64 * b0, 64 * (b1 - b0), fp, before, int(a.bases), int(a.sequences), Cs, 0, C.byref(out)))
     w = gpu.Index(out)
     assert 0 < int(gpu.capi.lib().bwtm_index_record_bytes(w.h)) <= 64 * ((50000 >> 7) - (1000 >> 7) + 4)
     with pytest.raises(gpu.BwtmError):
