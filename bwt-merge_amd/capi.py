@@ -176,6 +176,16 @@ SYMBOLS = [
     ("bwtm_correct_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, p_u8, p_u8, p_u32]),
     ("bwtm_correct_sequences", C.c_int, [vp, vp, p_u64, u64, u64, u64, C.c_uint32, p_u64, p_u8, u64, p_u8, p_u32]),
     ("bwtm_correct_stats", C.c_int, [p_u64]),
+    ("bwtm_unitigs_create", C.c_int, [vp, C.c_uint32, u64, C.POINTER(vp)]),
+    ("bwtm_unitigs_free", None, [vp]),
+    ("bwtm_unitigs_count", u64, [vp]),
+    ("bwtm_unitigs_nodes", u64, [vp]),
+    ("bwtm_unitigs_symbols", u64, [vp]),
+    ("bwtm_unitigs_bytes", u64, [vp]),
+    ("bwtm_unitigs_k", C.c_uint32, [vp]),
+    ("bwtm_unitigs_download", C.c_int, [vp, u64, u64, p_u64, p_u8, u64, p_u64, p_u64, p_u8, p_u64]),
+    ("bwtm_unitigs_place", C.c_int, [vp, p_u64, u64, p_u64, p_u64]),
+    ("bwtm_unitigs_stats", C.c_int, [p_u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
@@ -983,6 +993,12 @@ class Kmers:
         self._live()
         return Corrector(self, threshold, skip)
 
+    def unitigs(self, threshold, skip=5):
+        """The unitigs of the k-mer graph over the k-mers of count >= threshold (bwtm_unitigs_create); skip = the comp of N, the one the
+        k-mers were made with.  The graph copies what it needs: these k-mers may be freed at once."""
+        self._live()
+        return Unitigs(self, threshold, skip)
+
 
 CORRECT_CLEAN, CORRECT_CORRECTED, CORRECT_FAILED, CORRECT_SHORT = 0, 1, 2, 3
 CORRECT_STATS = ("lookups", "rounds", "max_edits", "batches")
@@ -1059,6 +1075,79 @@ class Corrector:
     @staticmethod
     def correct_stats():
         return correct_stats()
+
+
+UNITIG_CIRCULAR = 1
+UNITIG_NONE = (1 << 64) - 1
+UNITIG_STATS = ("lookups", "longest", "circular_nodes", "jump_rounds")
+
+
+class Unitigs:
+    """The compacted de Bruijn graph over the solid k-mers of a spectrum, on the device (handle on bwtm_unitigs)."""
+
+    def __init__(self, kmers, threshold, skip=5):
+        out = vp()
+        check(lib().bwtm_unitigs_create(kmers.h, int(skip), int(threshold), C.byref(out)))
+        self.h = out
+        self.skip, self.threshold = int(skip), max(int(threshold), 1)
+
+    count = property(lambda s: int(lib().bwtm_unitigs_count(s.h)))
+    nodes = property(lambda s: int(lib().bwtm_unitigs_nodes(s.h)))
+    symbols = property(lambda s: int(lib().bwtm_unitigs_symbols(s.h)))
+    bytes = property(lambda s: int(lib().bwtm_unitigs_bytes(s.h)))
+    k = property(lambda s: int(lib().bwtm_unitigs_k(s.h)))
+
+    def free(self):
+        if self.h:
+            lib().bwtm_unitigs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h:
+            raise BwtmError("the unitigs have been freed")
+
+    def download(self, first=0, count=None):
+        """(offsets uint64 [count + 1], text uint8, nodes, occurrences uint64 [count], flags uint8 [count], links uint64 [count, 4]) of the
+        unitigs [first, first + count) (count=None: up to the last one): the sizing call, then the filling call.  Unitig first + j has the
+        text text[offsets[j]: offsets[j + 1]] (comp values); a link is a unitig's number in the whole graph or UNITIG_NONE."""
+        self._live()
+        if count is None:
+            count = max(self.count - int(first), 0)
+        first, count = int(first), int(count)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        check(lib().bwtm_unitigs_download(self.h, first, count, offsets.ctypes.data_as(p_u64), None, 0, None, None, None, None))     # the size
+        text = np.zeros(int(offsets[-1]), dtype=np.uint8)
+        nodes, occurrences = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint64)
+        flags, links = np.zeros(count, dtype=np.uint8), np.zeros((count, 4), dtype=np.uint64)
+        check(lib().bwtm_unitigs_download(self.h, first, count, offsets.ctypes.data_as(p_u64), text.ctypes.data_as(p_u8) if text.size else None, text.size,
+                                          nodes.ctypes.data_as(p_u64), occurrences.ctypes.data_as(p_u64), flags.ctypes.data_as(p_u8), links.ctypes.data_as(p_u64)))
+        return offsets, text, nodes, occurrences, flags, links
+
+    def place(self, codes):
+        """(unitig, offset) uint64 arrays: where each code sits in the graph, UNITIG_NONE twice for a code that is no node."""
+        self._live()
+        codes, cp = _u64(codes)
+        unitig, offset = np.zeros(codes.size, dtype=np.uint64), np.zeros(codes.size, dtype=np.uint64)
+        check(lib().bwtm_unitigs_place(self.h, cp, codes.size, unitig.ctypes.data_as(p_u64), offset.ctypes.data_as(p_u64)))
+        return unitig, offset
+
+    @staticmethod
+    def stats():
+        return unitigs_stats()
+
+
+def unitigs_stats():
+    """What the calling thread's last bwtm_unitigs_create did (bwtm_unitigs_stats): table lookups, the longest unitig in nodes, nodes in
+    circular unitigs, rounds of pointer jumping."""
+    stats = np.zeros(4, dtype=np.uint64)
+    check(lib().bwtm_unitigs_stats(stats.ctypes.data_as(p_u64)))
+    return dict(zip(UNITIG_STATS, (int(v) for v in stats)))
 
 
 def correct_stats():

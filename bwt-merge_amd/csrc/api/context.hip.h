@@ -114,6 +114,7 @@ struct Tuning
   long long mem_batch = 1ll << 20;        // bwtm_matching_stats_batch / bwtm_mem_batch: patterns per batch (at most 2^28; bounds the device memory beyond the index: text, 20 bytes of statistics and 8 of flags per symbol, one batch of MEMs)
   long long approx_batch = 1ll << 16;     // bwtm_find_approx_batch: patterns per batch (at most 2^28; bounds the device memory beyond the index: a frontier's size is known only once it has been counted)
   long long correct_batch = 1ll << 20;    // bwtm_correct_*: reads per batch (at most 2^28; bounds the device memory beyond the table and the index: two copies of the text, offsets, status, edits)
+  long long unitig_launch = 1ll << 31;    // bwtm_unitigs_create: nodes per launch of its one-lane-per-node kernels (at most 2^31; tests use small values: larger graphs take several launches per phase)
   long long ingest_verify = 0;            // 1 = the builder checks every leaf's suffix order against the reads (one extra pass of gathers per leaf)
 #ifdef BWTM_DIAGNOSTICS
   long long walk_emit = 0;       // 0 = real emit; 1 / 2 timing-only variants of the emit (see diagnostics.hip.h)
@@ -741,6 +742,7 @@ int tune_set(const char* key, long long value)
   else if(k == "mem_batch") { g_tune.mem_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
   else if(k == "approx_batch") { g_tune.approx_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 16)); }
   else if(k == "correct_batch") { g_tune.correct_batch = (value > 0 ? std::min<long long>(value, 1ll << 28) : (1ll << 20)); }
+  else if(k == "unitig_launch") { g_tune.unitig_launch = (value > 0 ? std::min<long long>(value, 1ll << 31) : (1ll << 31)); }
   else if(k == "part_capacity") { g_tune.part_capacity = value; }
   else if(k == "recs_uniform") { g_tune.recs_uniform = (value > 0 ? 1 : (value < 0 ? -1 : 0)); }
   else if(k == "recs_window") { g_tune.recs_window = (value == 8192 || value == 16384 || value == 32768 ? value : 0); }

@@ -28,6 +28,8 @@
     api/edit.hip.h      patterns within edit distance e: the same frontier with a band of the edit-distance matrix per node, the hits gathered per pattern and length (b)
     api/correct.hip.h   k-mer error correction of reads: the solid k-mers of a spectrum as a sorted table with a bucket directory, a wave per read,
                         on patterns from the host or on sequences extracted on the device, in batches of bounded device memory (b)
+    api/unitigs.hip.h   the unitigs of the k-mer graph over the solid k-mers of a spectrum: the corrector's table with the counts beside it, the
+                        phases of kernels/unitigs.hip.h, the result downloaded in slices, k-mers placed in it
     api/mem.hip.h       matching statistics and maximal exact matches of patterns: one backward search per symbol of a batch's text; for the MEMs a quad
                         per pattern that flags the ends that give one, two scans and one emit, in batches of bounded device memory (b)
     api/fslice.hip.h    one GPU's state of the sliced frontier search (only with -DBWTM_EXPERIMENTAL; include/bwtm_experimental.h)
@@ -78,4 +80,5 @@ using namespace bwtm;
 #include "api/approx.hip.h"
 #include "api/edit.hip.h"
 #include "api/correct.hip.h"
+#include "api/unitigs.hip.h"
 #include "api/mem.hip.h"

@@ -73,6 +73,11 @@
                        k-mer error correction of reads: the codes of the solid k-mers compacted out of a spectrum, a bucket directory over
                        their top bits, and one wave per read that looks its windows up 64 at a time, finds the uncovered positions from a
                        ballot and substitutes one symbol per round (kernels/correct.hip.h; no counterpart in the reference)
+    k_unitig_counts, k_unitig_links, k_unitig_next, k_unitig_walk, k_unitig_unreached, k_unitig_cycle_init, k_unitig_cycle_jump,
+    k_unitig_cycle_starts, k_unitig_number, k_unitig_text, k_unitig_fill_links, k_unitig_place
+                       the unitigs of the k-mer graph over that table: degrees and the one compactable successor per node, a walk per
+                       path start, pointer jumping for the smallest node of a pure cycle, two scans that number the unitigs and place
+                       their text, the links of their last nodes (kernels/unitigs.hip.h; no counterpart in the reference)
 */
 #pragma once
 
@@ -130,6 +135,7 @@ __device__ inline void nt_store(u32* p, u32 v) { __builtin_nontemporal_store(v, 
 #include "kernels/approx.hip.h"
 #include "kernels/edit.hip.h"
 #include "kernels/correct.hip.h"
+#include "kernels/unitigs.hip.h"
 #ifdef BWTM_DIAGNOSTICS
 #include "kernels/diagnostics.hip.h"
 #endif

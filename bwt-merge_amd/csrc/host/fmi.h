@@ -363,6 +363,7 @@ public:
   size_type distinct() const { return bwtm_kmers_distinct(this->handle); }
   size_type total() const { return bwtm_kmers_total(this->handle); }
   size_type bytes() const { return bwtm_kmers_bytes(this->handle); }
+  const bwtm_kmers* device() const { return this->handle; }       // for the calls of include/bwtm.h that take the k-mers (bwt_unitigs)
 
   // The entries [first, first + count) in ascending order; sp may be null.
   void download(size_type first, size_type count, std::vector<uint64_t>& codes, std::vector<uint64_t>& counts, std::vector<uint64_t>* sp = nullptr) const

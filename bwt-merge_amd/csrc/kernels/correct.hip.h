@@ -80,6 +80,30 @@ __device__ inline bool correct_lookup(const CorrectTable& t, u64 code)
   return lo < end && t.codes[lo] == code;
 }
 
+// The index of the first entry >= code, t.solid when there is none (kernels/unitigs.hip.h).  The search stays inside the bucket of
+// `code`, clamped as above; when the bucket holds no such entry the answer is its end, dir[b + 1], which is the first entry of the later
+// buckets: the bucket's lower bound is the table's.  code must lie below 4^k, so that its bucket exists.
+__device__ inline u64 correct_lower_bound(const CorrectTable& t, u64 code)
+{
+  const u64 b = code >> (2 * t.k - t.dir_bits);
+  u64 lo = t.dir[b], hi = t.dir[b + 1];
+  if(hi > t.solid) { hi = t.solid; }
+  if(lo > hi) { lo = hi; }
+  while(lo < hi)
+  {
+    const u64 mid = lo + ((hi - lo) >> 1);
+    if(t.codes[mid] < code) { lo = mid + 1; } else { hi = mid; }
+  }
+  return lo;
+}
+
+// correct_lookup that says where: the index of the entry that holds `code`, ~0 when none does.
+__device__ inline u64 correct_index(const CorrectTable& t, u64 code)
+{
+  const u64 at = correct_lower_bound(t, code);
+  return (at < t.solid && t.codes[at] == code ? at : ~0ull);
+}
+
 // flags[i] = (cnt[i] >= threshold) for i < n, flags[n] = 0: the exclusive scan of the n + 1 flags gives every kept code its slot and,
 // in its last entry, the number of solid k-mers.
 __global__ void __launch_bounds__(BLOCK_THREADS) k_correct_flag(const u64* cnt, u64 n, u64 threshold, u64* flags)

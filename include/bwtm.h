@@ -458,6 +458,62 @@ int bwtm_correct_sequences(const bwtm_corrector* corrector, const bwtm_index* in
    most edits in one read, stats[3] = batches. */
 int bwtm_correct_stats(uint64_t stats[4]);
 
+/* The unitigs of the k-mer graph, the step of an assembler behind counting and correcting: the compacted de Bruijn graph over the
+   solid k-mers of a spectrum, with its coverage and links, built on the device.  k (1..32), `skip` (the comp of N), the codes and
+   the counts are those of bwtm_kmers_create; threshold t >= 1 (0 is taken as 1).  Reverse complements are not looked at: an index
+   that holds both strands gives them.
+   NODES.  The k-mers of the handle with count >= t: S of them, in ascending code order; node index = rank in that order.
+   EDGES.  x -> y when both are nodes and the last k - 1 symbols of x are the first k - 1 of y (k = 1: every node has an edge to
+   every node).  out(x) and in(x) are the numbers of such edges, 0..4; a self-loop counts in both.  An edge x -> y is COMPACTABLE
+   when out(x) == 1 and in(y) == 1.  Every node therefore has at most one compactable edge in and one out: the compactable edges
+   form disjoint paths and disjoint cycles.
+   UNITIGS.  Each path is one unitig; a single node with no compactable edge is a path of one.  Each cycle is one unitig with
+   BWTM_UNITIG_CIRCULAR set; it begins at the cycle's node of smallest code and runs once around.  Every node lies in exactly one
+   unitig, at exactly one offset.  A unitig of n nodes has a text of n + k - 1 comp values: the first node's k symbols, then the
+   last symbol of every further node (for a circular unitig the last k - 1 symbols repeat the first k - 1).  Its occurrences are
+   the sum of its nodes' counts.  Unitigs are numbered in ascending code order of their first node: U of them.
+   LINKS.  links[4 u + r] is the unitig that BEGINS with the node reached from unitig u's last node by appending the kept symbol
+   of rank r (the r-th of the four comp values other than skip), UINT64_MAX when that k-mer is not a node.  Every non-compactable
+   edge x -> y has x last in its unitig and y first in its unitig, so the links of all unitigs are all the non-compactable edges of
+   the graph.  A circular unitig has four UINT64_MAX.  A unitig may link to itself: a cycle entered by a tail is a linear unitig
+   that begins at the join node, and its last node links back to it.
+   The handle COPIES what it needs out of the k-mer handle, which may be freed at once.  A k-mer handle created with a min_count
+   above the threshold simply lacks the k-mers below min_count: they are no nodes.  `skip` MUST be the skip the k-mer handle was
+   created with (the handle does not record it).  S == 0 is valid and gives U == 0.  Two runs give the same bytes.
+   Memory (api/unitigs.hip.h derives both).  With Y = bwtm_unitigs_symbols = S + (k - 1) U and D = min(2 k, 24, max(1, ceil(log2 S)))
+   the handle keeps H = 8 max(S, 1) + 8 (2^D + 1) + 16 S + 57 U + 8 + Y bytes in ten blocks -- the corrector's table of the nodes,
+   unitig and offset of every node, and per unitig the text offsets, node counts, occurrences, flags, links and the text -- plus
+   what the pool rounds up: bwtm_unitigs_bytes <= 9/8 (17/16 H + 2560).  bwtm_unitigs_create takes, handle included, at most
+   17/16 (H + 8 n + 25 S + 8 U + C + (n + 2 S + U) / 128) + 2^16 bytes of device memory while every block stays below 512 MiB: n =
+   the k-mers of the k-mer handle, C = 32 S when some node lies on a cycle of compactable edges only, else 0.  A result that
+   does not fit the device is BWTM_ENOMEM.  The time of the call grows with the longest unitig (one dependent load per node of
+   it): bwtm_unitigs_stats reports its length.
+   BWTM_EINVAL, bwtm_last_error() naming the first offender: a null argument (the handle, `out`, the codes of a place call), skip
+   outside 1..5, first + count beyond U (a sum that wraps included), a capacity that is too small. */
+#define BWTM_UNITIG_CIRCULAR 1
+typedef struct bwtm_unitigs bwtm_unitigs;
+int bwtm_unitigs_create(const bwtm_kmers* kmers, uint32_t skip, uint64_t threshold, bwtm_unitigs** out);
+void bwtm_unitigs_free(bwtm_unitigs* unitigs);
+uint64_t bwtm_unitigs_count(const bwtm_unitigs* unitigs);      /* U */
+uint64_t bwtm_unitigs_nodes(const bwtm_unitigs* unitigs);      /* S */
+uint64_t bwtm_unitigs_symbols(const bwtm_unitigs* unitigs);    /* the sum of n_u + k - 1 */
+uint64_t bwtm_unitigs_bytes(const bwtm_unitigs* unitigs);      /* device bytes the handle holds */
+uint32_t bwtm_unitigs_k(const bwtm_unitigs* unitigs);
+/* The unitigs [first, first + count): offsets (count + 1 entries, starting at 0: unitig first + j has the text
+   text[offsets[j] .. offsets[j + 1])), text (capacity >= offsets[count]), nodes, occurrences and flags (count entries each), links
+   (4 per unitig, numbered in the whole graph).  Every output may be NULL.  text == NULL or capacity == 0 is a sizing call: the
+   other outputs are filled, no text comes back.  The range and the capacity are checked before anything is written: a refused
+   download writes nothing. */
+int bwtm_unitigs_download(const bwtm_unitigs* unitigs, uint64_t first, uint64_t count, uint64_t* offsets, uint8_t* text,
+                          uint64_t capacity, uint64_t* nodes, uint64_t* occurrences, uint8_t* flags, uint64_t* links);
+/* Where k-mers sit in the graph: unitig[j] and offset[j] = the unitig of codes[j] and the offset of that node in it, UINT64_MAX
+   twice for a code that is no node (a code of 4^k or more among them).  Either output may be NULL. */
+int bwtm_unitigs_place(const bwtm_unitigs* unitigs, const uint64_t* codes, uint64_t count, uint64_t* unitig, uint64_t* offset);
+/* What the calling thread's last bwtm_unitigs_create did: stats[0] = table lookups, stats[1] = the longest unitig in nodes,
+   stats[2] = nodes in circular unitigs, stats[3] = rounds of pointer jumping (0 when no node lies on a cycle of compactable
+   edges only). */
+int bwtm_unitigs_stats(uint64_t stats[4]);
+
 /* --- rank array: buildRA + mergeRA + RankArray (fmi.cpp:139-334, support.h:576-638) ---- */
 
 /* An empty rank array for inserting `b` into `a`. */
