@@ -3,6 +3,7 @@ language would write).  There is no CPU fallback: if libbwtm
 missing or no GPU is usable, calls raise."""
 import ctypes as C
 import os
+from functools import partial
 
 import numpy as np
 
@@ -17,6 +18,31 @@ p_u32 = C.POINTER(C.c_uint32)
 p_u64 = C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
+
+class _ArrayArg:
+    """Argument type of a `T*` parameter that takes the numpy array itself, so that the owner and the pointer are one object: None, a
+    C-contiguous array of exactly `dtype`, or whatever the plain pointer type takes (a pointer, a ctypes array, a byref).  Anything else is a
+    TypeError, which ctypes raises as ArgumentError before the library is entered."""
+
+    @classmethod
+    def from_param(cls, x):
+        if not isinstance(x, np.ndarray):
+            return cls.pointer.from_param(x)
+        if x.dtype != cls.dtype or not x.flags["C_CONTIGUOUS"]:
+            raise TypeError("a C-contiguous %s array is wanted, not %s%s" % (cls.dtype, x.dtype, "" if x.flags["C_CONTIGUOUS"] else " (not contiguous)"))
+        return x.ctypes.data_as(cls.pointer)
+
+
+class a_u8(_ArrayArg):
+    dtype, pointer = np.dtype(np.uint8), p_u8
+
+
+class a_u32(_ArrayArg):
+    dtype, pointer = np.dtype(np.uint32), p_u32
+
+
+class a_u64(_ArrayArg):
+    dtype, pointer = np.dtype(np.uint64), p_u64
 
 
 class HostInput(C.Structure):
@@ -81,28 +107,28 @@ SYMBOLS = [
     ("bwtm_device_bytes_peak", u64, [C.c_int]),
     ("bwtm_host_alloc", C.c_int, [u64, C.POINTER(vp)]),
     ("bwtm_host_free", None, [vp]),
-    ("bwtm_ra_download_runs", C.c_int, [vp, p_u64, p_u64, u64, p_u64]),
+    ("bwtm_ra_download_runs", C.c_int, [vp, a_u64, a_u64, u64, a_u64]),
     ("bwtm_ra_or_from", C.c_int, [vp, vp, u64]),
     ("bwtm_merge_consume", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_merged_records", u64, [vp, vp]),
-    ("bwtm_slice_bounds", C.c_int, [u64, C.c_int, C.c_int, p_u64, p_u64]),
-    ("bwtm_slice_bounds_equal", C.c_int, [u64, C.c_int, C.c_int, p_u64, p_u64, p_u64]),
-    ("bwtm_ra_range_counts", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64]),
-    ("bwtm_ra_finalize_range", C.c_int, [vp, u64, u64, u64, u64, p_u64, p_u64]),
+    ("bwtm_slice_bounds", C.c_int, [u64, C.c_int, C.c_int, a_u64, a_u64]),
+    ("bwtm_slice_bounds_equal", C.c_int, [u64, C.c_int, C.c_int, a_u64, a_u64, a_u64]),
+    ("bwtm_ra_range_counts", C.c_int, [vp, u64, u64, a_u64, a_u64, a_u64]),
+    ("bwtm_ra_finalize_range", C.c_int, [vp, u64, u64, u64, u64, a_u64, a_u64]),
     ("bwtm_interleave_range", C.c_int, [vp, vp, vp, u64, u64, C.POINTER(vp)]),
     ("bwtm_slice_free", None, [vp]),
-    ("bwtm_slice_lasthead", C.c_int, [vp, p_u64]),
-    ("bwtm_slice_size_table", C.c_int, [vp, u64, p_u64]),
-    ("bwtm_fold_offsets", C.c_int, [p_u64, C.c_int, p_u64]),
+    ("bwtm_slice_lasthead", C.c_int, [vp, a_u64]),
+    ("bwtm_slice_size_table", C.c_int, [vp, u64, a_u64]),
+    ("bwtm_fold_offsets", C.c_int, [a_u64, C.c_int, a_u64]),
     ("bwtm_slice_encode", C.c_int, [vp, u64]),
     ("bwtm_slice_byte_first", u64, [vp]),
     ("bwtm_slice_bytes", u64, [vp]),
     ("bwtm_slice_block_first", u64, [vp]),
     ("bwtm_slice_blocks", u64, [vp]),
-    ("bwtm_slice_first_block_start", C.c_int, [vp, p_u64]),
-    ("bwtm_slice_download_data", C.c_int, [vp, p_u8, u64]),
-    ("bwtm_slice_download_samples", C.c_int, [vp, u64, p_u64, p_u64]),
-    ("bwtm_slice_extract", C.c_int, [vp, u64, u64, p_u8]),
+    ("bwtm_slice_first_block_start", C.c_int, [vp, a_u64]),
+    ("bwtm_slice_download_data", C.c_int, [vp, a_u8, u64]),
+    ("bwtm_slice_download_samples", C.c_int, [vp, u64, a_u64, a_u64]),
+    ("bwtm_slice_extract", C.c_int, [vp, u64, u64, a_u8]),
     ("bwtm_merge_host", C.c_int, [C.POINTER(HostInput), C.POINTER(HostInput), ALLOC_FN, vp, C.c_int, C.POINTER(HostOutput), C.POINTER(vp)]),
     ("bwtm_merge_host_chained", C.c_int, [vp, C.POINTER(HostInput), ALLOC_FN, vp, C.c_int, C.POINTER(HostOutput), C.POINTER(vp)]),
     ("bwtm_merge_host_pipelined", C.c_int, [vp, C.POINTER(HostInput), C.POINTER(HostInput), vp, C.POINTER(HostInput), C.POINTER(vp), ALLOC_FN, vp, C.c_int,
@@ -116,66 +142,66 @@ SYMBOLS = [
     ("bwtm_synchronize", C.c_int, []),
     ("bwtm_trim", C.c_int, []),
     ("bwtm_tune", C.c_int, [C.c_char_p, C.c_longlong]),
-    ("bwtm_index_upload", C.c_int, [p_u8, u64, u64, u64, p_u64, C.POINTER(vp)]),
-    ("bwtm_index_upload_streamed", C.c_int, [p_u8, u64, u64, u64, p_u64, C.POINTER(vp), C.POINTER(UploadStats)]),
-    ("bwtm_index_from_device", C.c_int, [vp, u64, u64, u64, p_u64, C.POINTER(vp)]),
-    ("bwtm_index_from_device_borrowed", C.c_int, [vp, u64, u64, u64, p_u64, C.POINTER(vp)]),
+    ("bwtm_index_upload", C.c_int, [a_u8, u64, u64, u64, a_u64, C.POINTER(vp)]),
+    ("bwtm_index_upload_streamed", C.c_int, [a_u8, u64, u64, u64, a_u64, C.POINTER(vp), C.POINTER(UploadStats)]),
+    ("bwtm_index_from_device", C.c_int, [vp, u64, u64, u64, a_u64, C.POINTER(vp)]),
+    ("bwtm_index_from_device_borrowed", C.c_int, [vp, u64, u64, u64, a_u64, C.POINTER(vp)]),
     ("bwtm_index_from_symbols_device", C.c_int, [vp, u64, C.POINTER(vp)]),
     ("bwtm_index_free", None, [vp]),
     ("bwtm_index_bases", u64, [vp]),
     ("bwtm_index_sequences", u64, [vp]),
     ("bwtm_index_bytes", u64, [vp]),
     ("bwtm_index_blocks", u64, [vp]),
-    ("bwtm_index_C", None, [vp, p_u64]),
+    ("bwtm_index_C", None, [vp, a_u64]),
     ("bwtm_index_encode", C.c_int, [vp]),
     ("bwtm_index_drop_native", C.c_int, [vp]),
-    ("bwtm_index_device_data", C.c_int, [vp, C.POINTER(vp), p_u64]),
-    ("bwtm_index_download_data", C.c_int, [vp, p_u8, u64]),
-    ("bwtm_index_download_samples", C.c_int, [vp, p_u64, p_u64]),
+    ("bwtm_index_device_data", C.c_int, [vp, C.POINTER(vp), a_u64]),
+    ("bwtm_index_download_data", C.c_int, [vp, a_u8, u64]),
+    ("bwtm_index_download_samples", C.c_int, [vp, a_u64, a_u64]),
     ("bwtm_index_samples_width", C.c_int, [vp, C.POINTER(C.c_int)]),
-    ("bwtm_index_download_samples_compact", C.c_int, [vp, C.c_int, vp, p_u64]),
-    ("bwtm_rank_batch", C.c_int, [vp, p_u64, p_u8, u64, p_u64]),
-    ("bwtm_inverse_select_batch", C.c_int, [vp, p_u64, u64, p_u64, p_u8]),
-    ("bwtm_find_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u64, p_u64]),
-    ("bwtm_find_approx_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, u64, p_u64, p_u64, p_u64, p_u8, u64]),
-    ("bwtm_find_approx_stats", C.c_int, [p_u64]),
-    ("bwtm_find_edit_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, u64, p_u64, p_u64, p_u64, p_u8, p_u32, u64]),
-    ("bwtm_find_edit_stats", C.c_int, [p_u64]),
-    ("bwtm_matching_stats_batch", C.c_int, [vp, p_u8, p_u64, u64, p_u32, p_u64, p_u64]),
-    ("bwtm_mem_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, p_u64, p_u32, p_u32, p_u64, p_u64, u64]),
-    ("bwtm_mem_stats", C.c_int, [p_u64]),
-    ("bwtm_extract", C.c_int, [vp, u64, u64, p_u8]),
-    ("bwtm_sequences_extract", C.c_int, [vp, p_u64, u64, u64, u64, p_u64, p_u8, u64]),
+    ("bwtm_index_download_samples_compact", C.c_int, [vp, C.c_int, vp, a_u64]),
+    ("bwtm_rank_batch", C.c_int, [vp, a_u64, a_u8, u64, a_u64]),
+    ("bwtm_inverse_select_batch", C.c_int, [vp, a_u64, u64, a_u64, a_u8]),
+    ("bwtm_find_batch", C.c_int, [vp, a_u8, a_u64, u64, a_u64, a_u64]),
+    ("bwtm_find_approx_batch", C.c_int, [vp, a_u8, a_u64, u64, C.c_uint32, u64, a_u64, a_u64, a_u64, a_u8, u64]),
+    ("bwtm_find_approx_stats", C.c_int, [a_u64]),
+    ("bwtm_find_edit_batch", C.c_int, [vp, a_u8, a_u64, u64, C.c_uint32, u64, a_u64, a_u64, a_u64, a_u8, a_u32, u64]),
+    ("bwtm_find_edit_stats", C.c_int, [a_u64]),
+    ("bwtm_matching_stats_batch", C.c_int, [vp, a_u8, a_u64, u64, a_u32, a_u64, a_u64]),
+    ("bwtm_mem_batch", C.c_int, [vp, a_u8, a_u64, u64, C.c_uint32, a_u64, a_u32, a_u32, a_u64, a_u64, u64]),
+    ("bwtm_mem_stats", C.c_int, [a_u64]),
+    ("bwtm_extract", C.c_int, [vp, u64, u64, a_u8]),
+    ("bwtm_sequences_extract", C.c_int, [vp, a_u64, u64, u64, u64, a_u64, a_u8, u64]),
     ("bwtm_locator_create", C.c_int, [vp, u64, C.POINTER(vp)]),
     ("bwtm_locator_free", None, [vp]),
     ("bwtm_locator_bytes", u64, [vp]),
-    ("bwtm_locate_batch", C.c_int, [vp, p_u64, u64, p_u64, p_u64]),
-    ("bwtm_locate_ranges", C.c_int, [vp, p_u64, p_u64, u64, u64, p_u64, p_u64, p_u64, u64]),
-    ("bwtm_overlap_batch", C.c_int, [vp, p_u8, p_u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
-    ("bwtm_overlap_sequences", C.c_int, [vp, p_u64, u64, u64, u64, u64, p_u64, p_u64, p_u64, u64]),
+    ("bwtm_locate_batch", C.c_int, [vp, a_u64, u64, a_u64, a_u64]),
+    ("bwtm_locate_ranges", C.c_int, [vp, a_u64, a_u64, u64, u64, a_u64, a_u64, a_u64, u64]),
+    ("bwtm_overlap_batch", C.c_int, [vp, a_u8, a_u64, u64, u64, u64, a_u64, a_u64, a_u64, u64]),
+    ("bwtm_overlap_sequences", C.c_int, [vp, a_u64, u64, u64, u64, u64, a_u64, a_u64, a_u64, u64]),
     ("bwtm_kmers_create", C.c_int, [vp, C.c_uint32, C.c_uint32, u64, C.POINTER(vp)]),
     ("bwtm_kmers_free", None, [vp]),
     ("bwtm_kmers_distinct", u64, [vp]),
     ("bwtm_kmers_total", u64, [vp]),
     ("bwtm_kmers_bytes", u64, [vp]),
-    ("bwtm_kmers_levels", C.c_int, [vp, p_u64]),
-    ("bwtm_kmers_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64]),
-    ("bwtm_kmers_histogram", C.c_int, [vp, u64, p_u64]),
+    ("bwtm_kmers_levels", C.c_int, [vp, a_u64]),
+    ("bwtm_kmers_download", C.c_int, [vp, u64, u64, a_u64, a_u64, a_u64]),
+    ("bwtm_kmers_histogram", C.c_int, [vp, u64, a_u64]),
     ("bwtm_kmer_join_create", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u64, u64, u64, u64, u64, C.POINTER(vp)]),
     ("bwtm_kmer_join_free", None, [vp]),
     ("bwtm_kmer_join_distinct", u64, [vp]),
     ("bwtm_kmer_join_bytes", u64, [vp]),
-    ("bwtm_kmer_join_levels", C.c_int, [vp, p_u64]),
-    ("bwtm_kmer_join_download", C.c_int, [vp, u64, u64, p_u64, p_u64, p_u64, p_u64, p_u64]),
-    ("bwtm_kmer_join_summary", C.c_int, [vp, p_u64]),
+    ("bwtm_kmer_join_levels", C.c_int, [vp, a_u64]),
+    ("bwtm_kmer_join_download", C.c_int, [vp, u64, u64, a_u64, a_u64, a_u64, a_u64, a_u64]),
+    ("bwtm_kmer_join_summary", C.c_int, [vp, a_u64]),
     ("bwtm_corrector_create", C.c_int, [vp, C.c_uint32, u64, C.POINTER(vp)]),
     ("bwtm_corrector_free", None, [vp]),
     ("bwtm_corrector_solid", u64, [vp]),
     ("bwtm_corrector_bytes", u64, [vp]),
     ("bwtm_corrector_k", C.c_uint32, [vp]),
-    ("bwtm_correct_batch", C.c_int, [vp, p_u8, p_u64, u64, C.c_uint32, p_u8, p_u8, p_u32]),
-    ("bwtm_correct_sequences", C.c_int, [vp, vp, p_u64, u64, u64, u64, C.c_uint32, p_u64, p_u8, u64, p_u8, p_u32]),
-    ("bwtm_correct_stats", C.c_int, [p_u64]),
+    ("bwtm_correct_batch", C.c_int, [vp, a_u8, a_u64, u64, C.c_uint32, a_u8, a_u8, a_u32]),
+    ("bwtm_correct_sequences", C.c_int, [vp, vp, a_u64, u64, u64, u64, C.c_uint32, a_u64, a_u8, u64, a_u8, a_u32]),
+    ("bwtm_correct_stats", C.c_int, [a_u64]),
     ("bwtm_unitigs_create", C.c_int, [vp, C.c_uint32, u64, C.POINTER(vp)]),
     ("bwtm_unitigs_free", None, [vp]),
     ("bwtm_unitigs_count", u64, [vp]),
@@ -183,20 +209,20 @@ SYMBOLS = [
     ("bwtm_unitigs_symbols", u64, [vp]),
     ("bwtm_unitigs_bytes", u64, [vp]),
     ("bwtm_unitigs_k", C.c_uint32, [vp]),
-    ("bwtm_unitigs_download", C.c_int, [vp, u64, u64, p_u64, p_u8, u64, p_u64, p_u64, p_u8, p_u64]),
-    ("bwtm_unitigs_place", C.c_int, [vp, p_u64, u64, p_u64, p_u64]),
-    ("bwtm_unitigs_stats", C.c_int, [p_u64]),
+    ("bwtm_unitigs_download", C.c_int, [vp, u64, u64, a_u64, a_u8, u64, a_u64, a_u64, a_u8, a_u64]),
+    ("bwtm_unitigs_place", C.c_int, [vp, a_u64, u64, a_u64, a_u64]),
+    ("bwtm_unitigs_stats", C.c_int, [a_u64]),
     ("bwtm_ra_create", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_ra_buffer_bytes", u64, [vp, vp]),
     ("bwtm_ra_create_on", C.c_int, [vp, vp, vp, u64, C.POINTER(vp)]),
     ("bwtm_ra_free", None, [vp]),
     ("bwtm_search", C.c_int, [vp, vp, u64, u64, vp]),
-    ("bwtm_ra_device_buffer", C.c_int, [vp, C.POINTER(vp), p_u64]),
+    ("bwtm_ra_device_buffer", C.c_int, [vp, C.POINTER(vp), a_u64]),
     ("bwtm_ra_finalize", C.c_int, [vp]),
-    ("bwtm_ra_subset_check", C.c_int, [vp, vp, p_u64, p_u64]),
+    ("bwtm_ra_subset_check", C.c_int, [vp, vp, a_u64, a_u64]),
     ("bwtm_ra_values", u64, [vp]),
-    ("bwtm_ra_download", C.c_int, [vp, p_u64, u64]),
-    ("bwtm_ra_download_bits", C.c_int, [vp, p_u64, u64]),
+    ("bwtm_ra_download", C.c_int, [vp, a_u64, u64]),
+    ("bwtm_ra_download_bits", C.c_int, [vp, a_u64, u64]),
     ("bwtm_interleave", C.c_int, [vp, vp, vp, C.POINTER(vp)]),
     ("bwtm_merge", C.c_int, [vp, vp, C.POINTER(vp)]),
     ("bwtm_builder_create", C.c_int, [u64, C.POINTER(vp)]),
@@ -205,7 +231,7 @@ SYMBOLS = [
     ("bwtm_builder_finish", C.c_int, [vp, C.POINTER(vp)]),
     ("bwtm_builder_free", None, [vp]),
     ("bwtm_pool_stats", C.c_int, [vp]),
-    ("bwtm_pool_poison_stats", C.c_int, [p_u64, p_u64]),
+    ("bwtm_pool_poison_stats", C.c_int, [a_u64, a_u64]),
     ("bwtm_group_create", C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]),
     ("bwtm_group_free", None, [vp]),
     ("bwtm_group_part", C.c_int, [vp]),
@@ -213,23 +239,23 @@ SYMBOLS = [
     ("bwtm_group_barrier", C.c_int, [vp]),
     ("bwtm_group_allgather", C.c_int, [vp, vp, u64, vp]),
     ("bwtm_group_abort", None, [vp]),
-    ("bwtm_partition_cuts_host", C.c_int, [C.POINTER(HostIndex), C.POINTER(HostIndex), C.c_int, C.c_int, p_u64, p_u64]),
-    ("bwtm_window_blocks", C.c_int, [C.POINTER(HostIndex), u64, u64, p_u64, p_u64, p_u64, p_u64]),
-    ("bwtm_index_upload_window", C.c_int, [vp, u64, u64, p_u64, u64, u64, p_u64, C.c_int, C.POINTER(vp)]),
+    ("bwtm_partition_cuts_host", C.c_int, [C.POINTER(HostIndex), C.POINTER(HostIndex), C.c_int, C.c_int, a_u64, a_u64]),
+    ("bwtm_window_blocks", C.c_int, [C.POINTER(HostIndex), u64, u64, a_u64, a_u64, a_u64, a_u64]),
+    ("bwtm_index_upload_window", C.c_int, [vp, u64, u64, a_u64, u64, u64, a_u64, C.c_int, C.POINTER(vp)]),
     ("bwtm_index_record_bytes", u64, [vp]),
     ("bwtm_ra_create_range", C.c_int, [vp, vp, u64, u64, C.POINTER(vp)]),
     ("bwtm_ra_bytes", u64, [vp]),
-    ("bwtm_part_create", C.c_int, [vp, C.POINTER(IndexHeader), C.POINTER(IndexHeader), p_u64, p_u64, C.POINTER(vp)]),
+    ("bwtm_part_create", C.c_int, [vp, C.POINTER(IndexHeader), C.POINTER(IndexHeader), a_u64, a_u64, C.POINTER(vp)]),
     ("bwtm_part_free", None, [vp]),
-    ("bwtm_part_window", C.c_int, [vp, C.c_int, p_u64, p_u64]),
-    ("bwtm_part_upload", C.c_int, [vp, C.c_int, vp, u64, u64, p_u64, C.c_int]),
+    ("bwtm_part_window", C.c_int, [vp, C.c_int, a_u64, a_u64]),
+    ("bwtm_part_upload", C.c_int, [vp, C.c_int, vp, u64, u64, a_u64, C.c_int]),
     ("bwtm_part_search", C.c_int, [vp]),
-    ("bwtm_part_finish", C.c_int, [vp, C.POINTER(vp), p_u64, p_u64, p_u64]),
+    ("bwtm_part_finish", C.c_int, [vp, C.POINTER(vp), a_u64, a_u64, a_u64]),
     ("bwtm_part_stats", C.c_int, [vp, C.POINTER(PartInfo)]),
     ("bwtm_profile_enable", C.c_int, [C.c_int]),
     ("bwtm_profile_only", C.c_int, [C.c_char_p]),
     ("bwtm_profile_reset", C.c_int, []),
-    ("bwtm_profile_read", C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), p_u64, C.c_int]),
+    ("bwtm_profile_read", C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), a_u64, C.c_int]),
 ]
 
 
@@ -268,6 +294,88 @@ def check(rc):
         raise BwtmError("bwtm error %d: %s" % (rc, lib().bwtm_last_error().decode()))
 
 
+def _new(create, *args):
+    """The handle a create call makes: create(*args, &out), checked."""
+    out = vp()
+    check(create(*args, C.byref(out)))
+    return out
+
+
+class Handle:
+    """Base of the handle classes: h, released once through the C function the class names in _free.  _freed is the message of _live(),
+    for the classes whose methods check before they call.  A create call fills h in one line: self.h = _new(lib().bwtm_x_create, ...)."""
+    _free = _freed = h = None              # h = None: __del__ of an object made by __new__ finds nothing to free
+
+    def free(self):
+        if self.h:
+            getattr(lib(), self._free)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h:
+            raise BwtmError(self._freed)
+
+
+def _scalar(getter):
+    """A property that reads one number of a handle through the C function `getter`."""
+    return property(lambda s: int(getattr(lib(), getter)(s.h)))
+
+
+def _stats(call, names, *handle):
+    """The len(names) uint64 that call(*handle, stats) fills, by name."""
+    stats = np.zeros(len(names), dtype=np.uint64)
+    check(call(*handle, stats))
+    return dict(zip(names, (int(v) for v in stats)))
+
+
+def _u8(a):
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def pack_texts(patterns):
+    """A list of patterns (sequences of comp values) as the batch calls take them: (text uint8, offsets uint64 [len(patterns) + 1]);
+    pattern k is text[offsets[k]: offsets[k + 1]]."""
+    lens = np.array([len(p) for p in patterns], dtype=np.uint64)
+    offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(lens)
+    text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
+    return _u8(text), offsets
+
+
+def _size_then_fill(call, count, *dtypes):
+    """The sizing call, then the filling one: call(hit_offsets, *outputs, capacity) is a C call with its queries bound.  First with every
+    output None and capacity 0, which fills hit_offsets [count + 1]; then, only if there are hits, with arrays of exactly hit_offsets[-1]
+    entries of `dtypes`.  Returns (hit_offsets, *outputs)."""
+    hit_offsets = np.zeros(int(count) + 1, dtype=np.uint64)
+    check(call(hit_offsets, *[None] * len(dtypes), 0))
+    total = int(hit_offsets[-1])
+    outputs = [np.zeros(total, dtype=d) for d in dtypes]
+    if total > 0:
+        check(call(hit_offsets, *outputs, total))
+    return (hit_offsets, *outputs)
+
+
+def _ids_or_range(index, ids, first, count):
+    """(ids array or None, first, count) of a call whose queries are `ids` (any order, repeats allowed), or the sequences first .. first +
+    count - 1 of `index` (count=None: up to the last one)."""
+    if ids is not None:
+        ids = _u64(ids)
+        return ids, int(first), ids.size
+    if count is None:
+        count = max(index.sequences - int(first), 0)
+    return None, int(first), int(count)
+
+
 def init(device=0):
     check(lib().bwtm_init(device))
 
@@ -293,9 +401,7 @@ class Context:
     """An additional library context (device + streams + memory pool); make_current() binds the calling thread."""
 
     def __init__(self, device=0):
-        out = vp()
-        check(lib().bwtm_context_create(device, C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_context_create, device)
 
     def make_current(self):
         check(lib().bwtm_context_make_current(self.h))
@@ -316,9 +422,7 @@ class HostBuffer:
     def __init__(self, nbytes, dtype=np.uint8, ptr=None):
         self.nbytes = int(nbytes)
         if ptr is None:
-            out = vp()
-            check(lib().bwtm_host_alloc(self.nbytes, C.byref(out)))
-            ptr = out.value
+            ptr = _new(lib().bwtm_host_alloc, self.nbytes).value
         self.ptr = ptr
         raw = (C.c_uint8 * max(self.nbytes, 1)).from_address(self.ptr)
         self.array = np.frombuffer(raw, dtype=np.uint8)[: self.nbytes].view(dtype)
@@ -554,8 +658,9 @@ def merge_host_streamed(a, b, slice_records=0, samples=SAMPLES_COMPACT, chained=
     return data, width, x, y, out, stats
 
 
-class Upload:
+class Upload(Handle):
     """An input on its way to the device (bwtm_upload): keeps the host array alive until it is consumed."""
+    _free = "bwtm_upload_free"
 
     def __init__(self, handle, source):
         self.h, self.source = handle, source
@@ -563,29 +668,18 @@ class Upload:
     def finish(self):
         """-> Index (bwtm_upload_finish: waits for the copies, decodes, validates, transcodes)."""
         h, self.h = self.h, None
-        out = vp()
-        check(lib().bwtm_upload_finish(h, C.byref(out)))
+        out = _new(lib().bwtm_upload_finish, h)
         self.source = None
         return Index(out)
 
     def free(self):
-        if self.h is not None:
-            lib().bwtm_upload_free(self.h)
-            self.h = None
+        super().free()
         self.source = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def upload_begin(data, sequences, bases):
     hi = _host_input(data, sequences, bases)
-    out = vp()
-    check(lib().bwtm_upload_begin(C.byref(hi), C.byref(out)))
-    return Upload(out, data)
+    return Upload(_new(lib().bwtm_upload_begin, C.byref(hi)), data)
 
 
 def merge_host_pipelined(a=None, b=None, chained=None, pending=None, next=None, samples=True, keep=False, buffers=None):
@@ -629,16 +723,6 @@ def merge_host_pipelined(a=None, b=None, chained=None, pending=None, next=None, 
     return res, (Upload(np_, next[0]) if hn else None)
 
 
-def _u8(a):
-    a = np.ascontiguousarray(a, dtype=np.uint8)
-    return a, a.ctypes.data_as(p_u8)
-
-
-def _u64(a):
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    return a, a.ctypes.data_as(p_u64)
-
-
 class SequenceCount(int):
     """What Index.sequences gives: the number of sequences, as the int it has always been -- and, called,
     Index.sequences(ids=None, first=0, count=None, max_len=0) -> (offsets, text): the sequences themselves (Index.extract_sequences)."""
@@ -655,72 +739,50 @@ class SequenceCount(int):
         return (int, (int(self),))
 
 
-class Index:
+def _opt_u64(a):
+    return None if a is None else _u64(a)
+
+
+class Index(Handle):
     """Device-resident FM-index (handle on bwtm_index)."""
+    _free = "bwtm_index_free"
 
     def __init__(self, handle):
         self.h = vp(handle) if not isinstance(handle, vp) else handle
 
-    def free(self):
-        if self.h:
-            lib().bwtm_index_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
     @staticmethod
     def upload(data, sequences, bases, C_array=None):
-        data, dp = _u8(data)
-        out = vp()
-        cp = None
-        if C_array is not None:
-            C_array, cp = _u64(C_array)
-        check(lib().bwtm_index_upload(dp, data.size, sequences, bases, cp, C.byref(out)))
-        return Index(out)
+        data = _u8(data)
+        return Index(_new(lib().bwtm_index_upload, data, data.size, sequences, bases, _opt_u64(C_array)))
 
     @staticmethod
     def upload_streamed(data, sequences, bases, C_array=None):
         """bwtm_index_upload_streamed: the index (records and super table only) from chunks of the bytes, the stream never resident as a whole.
         Returns (Index, UploadStats)."""
-        data, dp = _u8(data)
-        out = vp()
-        cp = None
-        if C_array is not None:
-            C_array, cp = _u64(C_array)
-        stats = UploadStats()
-        check(lib().bwtm_index_upload_streamed(dp, data.size, sequences, bases, cp, C.byref(out), C.byref(stats)))
+        data = _u8(data)
+        out, stats = vp(), UploadStats()
+        check(lib().bwtm_index_upload_streamed(data, data.size, sequences, bases, _opt_u64(C_array), C.byref(out), C.byref(stats)))
         return Index(out), stats
 
     @staticmethod
     def from_device(ptr, nbytes, sequences, bases, C_array=None, borrow=False):
         """borrow=True: the index reads the caller's buffer in place (it must outlive the index)."""
-        out = vp()
-        cp = None
-        if C_array is not None:
-            C_array, cp = _u64(C_array)
         f = lib().bwtm_index_from_device_borrowed if borrow else lib().bwtm_index_from_device
-        check(f(vp(ptr), nbytes, sequences, bases, cp, C.byref(out)))
-        return Index(out)
+        return Index(_new(f, vp(ptr), nbytes, sequences, bases, _opt_u64(C_array)))
 
     @staticmethod
     def from_symbols_device(ptr, bases):
-        out = vp()
-        check(lib().bwtm_index_from_symbols_device(vp(ptr), bases, C.byref(out)))
-        return Index(out)
+        return Index(_new(lib().bwtm_index_from_symbols_device, vp(ptr), bases))
 
-    bases = property(lambda s: int(lib().bwtm_index_bases(s.h)))
+    bases = _scalar("bwtm_index_bases")
     sequences = property(lambda s: SequenceCount(lib().bwtm_index_sequences(s.h), s))
-    nbytes = property(lambda s: int(lib().bwtm_index_bytes(s.h)))
-    blocks = property(lambda s: int(lib().bwtm_index_blocks(s.h)))
+    nbytes = _scalar("bwtm_index_bytes")
+    blocks = _scalar("bwtm_index_blocks")
 
     @property
     def C(self):
         out = np.zeros(SIGMA + 1, dtype=np.uint64)
-        lib().bwtm_index_C(self.h, out.ctypes.data_as(p_u64))
+        lib().bwtm_index_C(self.h, out)
         return out
 
     def encode(self):
@@ -742,20 +804,20 @@ class Index:
 
     def data(self):
         out = np.zeros(self.nbytes, dtype=np.uint8)
-        check(lib().bwtm_index_download_data(self.h, out.ctypes.data_as(p_u8), out.size))
+        check(lib().bwtm_index_download_data(self.h, out, out.size))
         return out
 
     def download_into(self, out):
         """Native bytes into a caller's uint8 array (e.g. page-locked memory)."""
         assert out.dtype == np.uint8 and out.size >= self.nbytes
-        check(lib().bwtm_index_download_data(self.h, out.ctypes.data_as(p_u8), out.size))
+        check(lib().bwtm_index_download_data(self.h, out, out.size))
         return out
 
     def samples(self):
         nb = self.blocks
         be = np.zeros(nb, dtype=np.uint64)
         cum = np.zeros((SIGMA, nb + 1), dtype=np.uint64)
-        check(lib().bwtm_index_download_samples(self.h, be.ctypes.data_as(p_u64), cum.ctypes.data_as(p_u64)))
+        check(lib().bwtm_index_download_samples(self.h, be, cum))
         return be, cum
 
     def samples_compact(self, width=None):
@@ -769,140 +831,82 @@ class Index:
         nb = self.blocks
         fields = np.zeros((SIGMA, nb), dtype=FIELD_DTYPES[width])
         anchors = np.zeros((SIGMA, (nb + 63) // 64), dtype=np.uint64)
-        check(lib().bwtm_index_download_samples_compact(self.h, width, fields.ctypes.data_as(vp), anchors.ctypes.data_as(p_u64)))
+        check(lib().bwtm_index_download_samples_compact(self.h, width, fields.ctypes.data_as(vp), anchors))
         return width, fields, anchors
 
     def rank(self, positions, comps):
-        positions, pp = _u64(positions)
-        comps, cp = _u8(comps)
+        positions, comps = _u64(positions), _u8(comps)
         out = np.zeros(positions.size, dtype=np.uint64)
-        check(lib().bwtm_rank_batch(self.h, pp, cp, positions.size, out.ctypes.data_as(p_u64)))
+        check(lib().bwtm_rank_batch(self.h, positions, comps, positions.size, out))
         return out
 
     def inverse_select(self, positions):
-        positions, pp = _u64(positions)
+        positions = _u64(positions)
         r = np.zeros(positions.size, dtype=np.uint64)
         c = np.zeros(positions.size, dtype=np.uint8)
-        check(lib().bwtm_inverse_select_batch(self.h, pp, positions.size, r.ctypes.data_as(p_u64), c.ctypes.data_as(p_u8)))
+        check(lib().bwtm_inverse_select_batch(self.h, positions, positions.size, r, c))
         return r, c
 
     def find(self, patterns):
         """Backward search of a list of patterns (sequences of comp values); returns (sp, ep) arrays."""
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
+        text, offsets = pack_texts(patterns)
         sp = np.zeros(len(patterns), dtype=np.uint64)
         ep = np.zeros(len(patterns), dtype=np.uint64)
-        check(lib().bwtm_find_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), sp.ctypes.data_as(p_u64), ep.ctypes.data_as(p_u64)))
+        check(lib().bwtm_find_batch(self.h, text, offsets, len(patterns), sp, ep))
         return sp, ep
 
     def find_approx(self, patterns, max_mismatches, max_hits=0):
         """Backward search with up to max_mismatches substitutions (bwtm_find_approx_batch).  Returns (hit_offsets [count + 1], sp, count,
         mismatches): the hits of pattern k are [hit_offsets[k], hit_offsets[k + 1]), each the range [sp, sp + count - 1] of one matched
         string, ascending when those strings are compared from their last symbol backwards.  One sizing call, then the filling call."""
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
-        hit_offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        check(lib().bwtm_find_approx_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_mismatches), int(max_hits),
-                                           hit_offsets.ctypes.data_as(p_u64), None, None, None, 0))
-        total = int(hit_offsets[-1])
-        sp = np.zeros(total, dtype=np.uint64)
-        count = np.zeros(total, dtype=np.uint64)
-        mismatches = np.zeros(total, dtype=np.uint8)
-        if total > 0:
-            check(lib().bwtm_find_approx_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_mismatches), int(max_hits),
-                                               hit_offsets.ctypes.data_as(p_u64), sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64),
-                                               mismatches.ctypes.data_as(p_u8), total))
-        return hit_offsets, sp, count, mismatches
+        text, offsets = pack_texts(patterns)
+        return _size_then_fill(partial(lib().bwtm_find_approx_batch, self.h, text, offsets, len(patterns), int(max_mismatches), int(max_hits)),
+                               len(patterns), np.uint64, np.uint64, np.uint8)
 
     def find_edit(self, patterns, max_edits, max_hits=0):
         """Backward search within edit distance max_edits, indels included (bwtm_find_edit_batch).  Returns (hit_offsets [count + 1], sp,
         count, edits, lengths): the hits of pattern k are [hit_offsets[k], hit_offsets[k + 1]), each the range [sp, sp + count - 1] of one
         matched string of `lengths` symbols at distance `edits`, shortest first and, within a length, ascending when the strings are
         compared from their last symbol backwards.  One sizing call, then the filling call."""
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
-        hit_offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        check(lib().bwtm_find_edit_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_edits), int(max_hits),
-                                         hit_offsets.ctypes.data_as(p_u64), None, None, None, None, 0))
-        total = int(hit_offsets[-1])
-        sp = np.zeros(total, dtype=np.uint64)
-        count = np.zeros(total, dtype=np.uint64)
-        edits = np.zeros(total, dtype=np.uint8)
-        lengths = np.zeros(total, dtype=np.uint32)
-        if total > 0:
-            check(lib().bwtm_find_edit_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_edits), int(max_hits),
-                                             hit_offsets.ctypes.data_as(p_u64), sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64),
-                                             edits.ctypes.data_as(p_u8), lengths.ctypes.data_as(p_u32), total))
-        return hit_offsets, sp, count, edits, lengths
+        text, offsets = pack_texts(patterns)
+        return _size_then_fill(partial(lib().bwtm_find_edit_batch, self.h, text, offsets, len(patterns), int(max_edits), int(max_hits)),
+                               len(patterns), np.uint64, np.uint64, np.uint8, np.uint32)
 
     def matching_stats(self, patterns):
         """Matching statistics of a list of patterns (bwtm_matching_stats_batch).  Returns (lengths, sp, count), arrays over all symbols of
         the patterns in order: the entry of symbol i of pattern k, at sum(len(patterns[:k])) + i, is the longest match that ends with that
         symbol, lengths symbols long, and its range [sp, sp + count - 1]; (0, 0, 0) when the symbol alone does not occur."""
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
+        text, offsets = pack_texts(patterns)
         total = int(offsets[-1])
         lengths = np.zeros(total, dtype=np.uint32)
         sp = np.zeros(total, dtype=np.uint64)
         count = np.zeros(total, dtype=np.uint64)
-        check(lib().bwtm_matching_stats_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), lengths.ctypes.data_as(p_u32),
-                                              sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64)))
+        check(lib().bwtm_matching_stats_batch(self.h, text, offsets, len(patterns), lengths, sp, count))
         return lengths, sp, count
 
     def mems(self, patterns, min_length=1):
         """Maximal exact matches of a list of patterns (bwtm_mem_batch).  Returns (hit_offsets [count + 1], begin, length, sp, count): the
         MEMs of pattern k are [hit_offsets[k], hit_offsets[k + 1]), begins (and ends) ascending; MEM h is patterns[k][begin[h]: begin[h] +
         length[h]], length[h] >= min_length, and occurs at the positions [sp[h], sp[h] + count[h] - 1].  One sizing call, then the filling call."""
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
-        hit_offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        check(lib().bwtm_mem_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_length), hit_offsets.ctypes.data_as(p_u64),
-                                   None, None, None, None, 0))
-        total = int(hit_offsets[-1])
-        begin = np.zeros(total, dtype=np.uint32)
-        length = np.zeros(total, dtype=np.uint32)
-        sp = np.zeros(total, dtype=np.uint64)
-        count = np.zeros(total, dtype=np.uint64)
-        if total > 0:
-            check(lib().bwtm_mem_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_length), hit_offsets.ctypes.data_as(p_u64),
-                                       begin.ctypes.data_as(p_u32), length.ctypes.data_as(p_u32), sp.ctypes.data_as(p_u64), count.ctypes.data_as(p_u64), total))
-        return hit_offsets, begin, length, sp, count
+        text, offsets = pack_texts(patterns)
+        return _size_then_fill(partial(lib().bwtm_mem_batch, self.h, text, offsets, len(patterns), int(min_length)),
+                               len(patterns), np.uint32, np.uint32, np.uint64, np.uint64)
 
     def extract(self, first, count):
         out = np.zeros(count, dtype=np.uint8)
-        check(lib().bwtm_extract(self.h, first, count, out.ctypes.data_as(p_u8)))
+        check(lib().bwtm_extract(self.h, first, count, out))
         return out
 
     def extract_sequences(self, ids=None, first=0, count=None, max_len=0):
         """Index.sequences(...): sequences by id (bwtm_sequences_extract): ids = an array of ids in any order, repeats allowed, or None for the ids
         first .. first + count - 1 (count=None: up to the last sequence).  Returns (offsets uint64 [count + 1], text uint8): sequence j is
         text[offsets[j]: offsets[j + 1]], comp values 1..5 in forward order.  One sizing call, then the extracting call."""
-        ip = None
-        if ids is not None:
-            ids, ip = _u64(ids)
-            count = ids.size
-        elif count is None:
-            count = max(self.sequences - int(first), 0)
-        offsets = np.zeros(int(count) + 1, dtype=np.uint64)
-        check(lib().bwtm_sequences_extract(self.h, ip, int(first), int(count), int(max_len), offsets.ctypes.data_as(p_u64), None, 0))
+        ids, first, count = _ids_or_range(self, ids, first, count)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        check(lib().bwtm_sequences_extract(self.h, ids, first, count, int(max_len), offsets, None, 0))
         text = np.zeros(int(offsets[-1]), dtype=np.uint8)
         if text.size > 0:
-            check(lib().bwtm_sequences_extract(self.h, ip, int(first), int(count), int(max_len), offsets.ctypes.data_as(p_u64), text.ctypes.data_as(p_u8), text.size))
+            check(lib().bwtm_sequences_extract(self.h, ids, first, count, int(max_len), offsets, text, text.size))
         return offsets, text
 
     def locator(self, max_len=0):
@@ -934,39 +938,23 @@ def decode_kmers(codes, k, skip):
     return kmer_comps(skip)[((codes[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.int64)]
 
 
-class Kmers:
+class Kmers(Handle):
     """The kept k-mers of an index in ascending order, on the device (handle on bwtm_kmers).  It does not borrow the index."""
+    _free, _freed = "bwtm_kmers_free", "the k-mers have been freed"
 
     def __init__(self, index, k, skip=5, min_count=1):
-        out = vp()
-        check(lib().bwtm_kmers_create(index.h, int(k), int(skip), int(min_count), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_kmers_create, index.h, int(k), int(skip), int(min_count))
         self.k, self.skip = int(k), int(skip)
 
-    distinct = property(lambda s: int(lib().bwtm_kmers_distinct(s.h)))
-    total = property(lambda s: int(lib().bwtm_kmers_total(s.h)))
-    nbytes = property(lambda s: int(lib().bwtm_kmers_bytes(s.h)))
-
-    def free(self):
-        if self.h:
-            lib().bwtm_kmers_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def _live(self):
-        if not self.h:
-            raise BwtmError("the k-mers have been freed")
+    distinct = _scalar("bwtm_kmers_distinct")
+    total = _scalar("bwtm_kmers_total")
+    nbytes = _scalar("bwtm_kmers_bytes")
 
     def levels(self):
         """nodes[t] = distinct (t + 1)-mers with count >= min_count, t < k."""
         self._live()
         nodes = np.zeros(KMER_MAX_K, dtype=np.uint64)
-        check(lib().bwtm_kmers_levels(self.h, nodes.ctypes.data_as(p_u64)))
+        check(lib().bwtm_kmers_levels(self.h, nodes))
         return nodes[: self.k]
 
     def download(self, first=0, count=None):
@@ -977,14 +965,14 @@ class Kmers:
         if int(first) + int(count) > self.distinct:                      # the library says so, before arrays of that size are made
             check(lib().bwtm_kmers_download(self.h, int(first), int(count), None, None, None))
         codes, counts, sp = (np.zeros(int(count), dtype=np.uint64) for _ in range(3))
-        check(lib().bwtm_kmers_download(self.h, int(first), int(count), codes.ctypes.data_as(p_u64), counts.ctypes.data_as(p_u64), sp.ctypes.data_as(p_u64)))
+        check(lib().bwtm_kmers_download(self.h, int(first), int(count), codes, counts, sp))
         return codes, counts, sp
 
     def histogram(self, bins):
         """hist[j] = kept k-mers of count j, the last bin those of count >= bins - 1."""
         self._live()
         hist = np.zeros(max(int(bins), 0), dtype=np.uint64)
-        check(lib().bwtm_kmers_histogram(self.h, int(bins), hist.ctypes.data_as(p_u64)))
+        check(lib().bwtm_kmers_histogram(self.h, int(bins), hist))
         return hist
 
     def corrector(self, threshold, skip=5):
@@ -1004,48 +992,27 @@ CORRECT_CLEAN, CORRECT_CORRECTED, CORRECT_FAILED, CORRECT_SHORT = 0, 1, 2, 3
 CORRECT_STATS = ("lookups", "rounds", "max_edits", "batches")
 
 
-class Corrector:
+class Corrector(Handle):
     """The solid k-mers of a spectrum on the device, and the correction of reads against them (handle on bwtm_corrector)."""
+    _free, _freed = "bwtm_corrector_free", "the corrector has been freed"
 
     def __init__(self, kmers, threshold, skip=5):
-        out = vp()
-        check(lib().bwtm_corrector_create(kmers.h, int(skip), int(threshold), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_corrector_create, kmers.h, int(skip), int(threshold))
         self.skip, self.threshold = int(skip), max(int(threshold), 1)
 
-    solid = property(lambda s: int(lib().bwtm_corrector_solid(s.h)))
-    nbytes = property(lambda s: int(lib().bwtm_corrector_bytes(s.h)))
-    k = property(lambda s: int(lib().bwtm_corrector_k(s.h)))
-
-    def free(self):
-        if self.h:
-            lib().bwtm_corrector_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def _live(self):
-        if not self.h:
-            raise BwtmError("the corrector has been freed")
+    solid = _scalar("bwtm_corrector_solid")
+    nbytes = _scalar("bwtm_corrector_bytes")
+    k = _scalar("bwtm_corrector_k")
 
     def correct(self, patterns, max_rounds=10):
         """Reads from the host (bwtm_correct_batch): a list of sequences of comp values 1..5.  Returns (list of uint8 arrays, status
         uint8 [count], edits uint32 [count]); status is one of CORRECT_CLEAN / _CORRECTED / _FAILED / _SHORT."""
         self._live()
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
+        text, offsets = pack_texts(patterns)
         out = np.zeros(max(text.size, 1), dtype=np.uint8)
         status = np.zeros(len(patterns), dtype=np.uint8)
         edits = np.zeros(len(patterns), dtype=np.uint32)
-        check(lib().bwtm_correct_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(max_rounds), out.ctypes.data_as(p_u8),
-                                       status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+        check(lib().bwtm_correct_batch(self.h, text, offsets, len(patterns), int(max_rounds), out, status, edits))
         return [out[int(offsets[j]): int(offsets[j + 1])] for j in range(len(patterns))], status, edits
 
     def correct_sequences(self, index, ids=None, first=0, count=None, max_len=0, max_rounds=10, text=True):
@@ -1053,23 +1020,17 @@ class Corrector:
         Index.sequences.  Returns (offsets uint64 [count + 1], text uint8 or None, status, edits).  text=False: one status call.
         Otherwise the sizing call of bwtm_sequences_extract, then the filling call."""
         self._live()
-        ip = None
-        if ids is not None:
-            ids, ip = _u64(ids)
-            count = ids.size
-        elif count is None:
-            count = max(index.sequences - int(first), 0)
-        count = int(count)
+        ids, first, count = _ids_or_range(index, ids, first, count)
         offsets = np.zeros(count + 1, dtype=np.uint64)
         status = np.zeros(count, dtype=np.uint8)
         edits = np.zeros(count, dtype=np.uint32)
-        args = (self.h, index.h, ip, int(first), count, int(max_len), int(max_rounds), offsets.ctypes.data_as(p_u64))
+        args = (self.h, index.h, ids, first, count, int(max_len), int(max_rounds), offsets)
         if not text:
-            check(lib().bwtm_correct_sequences(*args, None, 0, status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+            check(lib().bwtm_correct_sequences(*args, None, 0, status, edits))
             return offsets, None, status, edits
-        check(lib().bwtm_sequences_extract(index.h, ip, int(first), count, int(max_len), offsets.ctypes.data_as(p_u64), None, 0))     # the size
+        check(lib().bwtm_sequences_extract(index.h, ids, first, count, int(max_len), offsets, None, 0))     # the size
         out = np.zeros(int(offsets[-1]), dtype=np.uint8)
-        check(lib().bwtm_correct_sequences(*args, out.ctypes.data_as(p_u8) if out.size else None, out.size, status.ctypes.data_as(p_u8), edits.ctypes.data_as(p_u32)))
+        check(lib().bwtm_correct_sequences(*args, out if out.size else None, out.size, status, edits))
         return offsets, out, status, edits
 
     @staticmethod
@@ -1082,35 +1043,19 @@ UNITIG_NONE = (1 << 64) - 1
 UNITIG_STATS = ("lookups", "longest", "circular_nodes", "jump_rounds")
 
 
-class Unitigs:
+class Unitigs(Handle):
     """The compacted de Bruijn graph over the solid k-mers of a spectrum, on the device (handle on bwtm_unitigs)."""
+    _free, _freed = "bwtm_unitigs_free", "the unitigs have been freed"
 
     def __init__(self, kmers, threshold, skip=5):
-        out = vp()
-        check(lib().bwtm_unitigs_create(kmers.h, int(skip), int(threshold), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_unitigs_create, kmers.h, int(skip), int(threshold))
         self.skip, self.threshold = int(skip), max(int(threshold), 1)
 
-    count = property(lambda s: int(lib().bwtm_unitigs_count(s.h)))
-    nodes = property(lambda s: int(lib().bwtm_unitigs_nodes(s.h)))
-    symbols = property(lambda s: int(lib().bwtm_unitigs_symbols(s.h)))
-    bytes = property(lambda s: int(lib().bwtm_unitigs_bytes(s.h)))
-    k = property(lambda s: int(lib().bwtm_unitigs_k(s.h)))
-
-    def free(self):
-        if self.h:
-            lib().bwtm_unitigs_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def _live(self):
-        if not self.h:
-            raise BwtmError("the unitigs have been freed")
+    count = _scalar("bwtm_unitigs_count")
+    nodes = _scalar("bwtm_unitigs_nodes")
+    symbols = _scalar("bwtm_unitigs_symbols")
+    bytes = _scalar("bwtm_unitigs_bytes")
+    k = _scalar("bwtm_unitigs_k")
 
     def download(self, first=0, count=None):
         """(offsets uint64 [count + 1], text uint8, nodes, occurrences uint64 [count], flags uint8 [count], links uint64 [count, 4]) of the
@@ -1121,20 +1066,19 @@ class Unitigs:
             count = max(self.count - int(first), 0)
         first, count = int(first), int(count)
         offsets = np.zeros(count + 1, dtype=np.uint64)
-        check(lib().bwtm_unitigs_download(self.h, first, count, offsets.ctypes.data_as(p_u64), None, 0, None, None, None, None))     # the size
+        check(lib().bwtm_unitigs_download(self.h, first, count, offsets, None, 0, None, None, None, None))     # the size
         text = np.zeros(int(offsets[-1]), dtype=np.uint8)
         nodes, occurrences = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint64)
         flags, links = np.zeros(count, dtype=np.uint8), np.zeros((count, 4), dtype=np.uint64)
-        check(lib().bwtm_unitigs_download(self.h, first, count, offsets.ctypes.data_as(p_u64), text.ctypes.data_as(p_u8) if text.size else None, text.size,
-                                          nodes.ctypes.data_as(p_u64), occurrences.ctypes.data_as(p_u64), flags.ctypes.data_as(p_u8), links.ctypes.data_as(p_u64)))
+        check(lib().bwtm_unitigs_download(self.h, first, count, offsets, text if text.size else None, text.size, nodes, occurrences, flags, links))
         return offsets, text, nodes, occurrences, flags, links
 
     def place(self, codes):
         """(unitig, offset) uint64 arrays: where each code sits in the graph, UNITIG_NONE twice for a code that is no node."""
         self._live()
-        codes, cp = _u64(codes)
+        codes = _u64(codes)
         unitig, offset = np.zeros(codes.size, dtype=np.uint64), np.zeros(codes.size, dtype=np.uint64)
-        check(lib().bwtm_unitigs_place(self.h, cp, codes.size, unitig.ctypes.data_as(p_u64), offset.ctypes.data_as(p_u64)))
+        check(lib().bwtm_unitigs_place(self.h, codes, codes.size, unitig, offset))
         return unitig, offset
 
     @staticmethod
@@ -1145,57 +1089,37 @@ class Unitigs:
 def unitigs_stats():
     """What the calling thread's last bwtm_unitigs_create did (bwtm_unitigs_stats): table lookups, the longest unitig in nodes, nodes in
     circular unitigs, rounds of pointer jumping."""
-    stats = np.zeros(4, dtype=np.uint64)
-    check(lib().bwtm_unitigs_stats(stats.ctypes.data_as(p_u64)))
-    return dict(zip(UNITIG_STATS, (int(v) for v in stats)))
+    return _stats(lib().bwtm_unitigs_stats, UNITIG_STATS)
 
 
 def correct_stats():
     """What the calling thread's last correct call did (bwtm_correct_stats): table lookups, rounds run over all reads, the most edits in one
     read, batches."""
-    stats = np.zeros(4, dtype=np.uint64)
-    check(lib().bwtm_correct_stats(stats.ctypes.data_as(p_u64)))
-    return dict(zip(CORRECT_STATS, (int(v) for v in stats)))
+    return _stats(lib().bwtm_correct_stats, CORRECT_STATS)
 
 
 KMER_JOIN_NO_BOUND = (1 << 64) - 1
 KMER_JOIN_STATS = ("only_a", "only_b", "both", "only_a_occurrences_a", "only_b_occurrences_b", "both_occurrences_a", "both_occurrences_b")
 
 
-class KmerJoin:
+class KmerJoin(Handle):
     """The kept k-mers of two indexes in ascending order with their counts and insertion points in each, on the device (handle on
     bwtm_kmer_join).  It does not borrow the indexes."""
+    _free, _freed = "bwtm_kmer_join_free", "the k-mer join has been freed"
 
     def __init__(self, a, b, k, skip=5, min_a=0, max_a=None, min_b=0, max_b=None, min_sum=1):
-        out = vp()
-        check(lib().bwtm_kmer_join_create(a.h, b.h, int(k), int(skip), int(min_a), KMER_JOIN_NO_BOUND if max_a is None else int(max_a),
-                                          int(min_b), KMER_JOIN_NO_BOUND if max_b is None else int(max_b), int(min_sum), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_kmer_join_create, a.h, b.h, int(k), int(skip), int(min_a), KMER_JOIN_NO_BOUND if max_a is None else int(max_a),
+                      int(min_b), KMER_JOIN_NO_BOUND if max_b is None else int(max_b), int(min_sum))
         self.k, self.skip = int(k), int(skip)
 
-    distinct = property(lambda s: int(lib().bwtm_kmer_join_distinct(s.h)))
-    nbytes = property(lambda s: int(lib().bwtm_kmer_join_bytes(s.h)))
-
-    def free(self):
-        if self.h:
-            lib().bwtm_kmer_join_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def _live(self):
-        if not self.h:
-            raise BwtmError("the k-mer join has been freed")
+    distinct = _scalar("bwtm_kmer_join_distinct")
+    nbytes = _scalar("bwtm_kmer_join_bytes")
 
     def levels(self):
         """nodes[t] = the (t + 1)-mers the lower bounds keep for t < k - 1; nodes[k - 1] = the result (upper bounds applied)."""
         self._live()
         nodes = np.zeros(KMER_MAX_K, dtype=np.uint64)
-        check(lib().bwtm_kmer_join_levels(self.h, nodes.ctypes.data_as(p_u64)))
+        check(lib().bwtm_kmer_join_levels(self.h, nodes))
         return nodes[: self.k]
 
     def download(self, first=0, count=None):
@@ -1206,68 +1130,46 @@ class KmerJoin:
         if int(first) + int(count) > self.distinct:                      # the library says so, before arrays of that size are made
             check(lib().bwtm_kmer_join_download(self.h, int(first), int(count), None, None, None, None, None))
         arrays = tuple(np.zeros(int(count), dtype=np.uint64) for _ in range(5))
-        check(lib().bwtm_kmer_join_download(self.h, int(first), int(count), *[a.ctypes.data_as(p_u64) for a in arrays]))
+        check(lib().bwtm_kmer_join_download(self.h, int(first), int(count), *arrays))
         return arrays
 
     def summary(self):
         """The seven numbers of bwtm_kmer_join_summary by name (KMER_JOIN_STATS)."""
         self._live()
-        stats = np.zeros(7, dtype=np.uint64)
-        check(lib().bwtm_kmer_join_summary(self.h, stats.ctypes.data_as(p_u64)))
-        return dict(zip(KMER_JOIN_STATS, (int(v) for v in stats)))
+        return _stats(lib().bwtm_kmer_join_summary, KMER_JOIN_STATS, self.h)
 
 
-class Locator:
+class Locator(Handle):
     """From BWT positions of an index to (sequence id, offset of the suffix in that sequence) (handle on bwtm_locator).  It keeps a reference to
     the index it borrows; free it before the index is consumed by a merge."""
+    _free, _freed = "bwtm_locator_free", "the locator has been freed"
 
     def __init__(self, index, max_len=0):
-        out = vp()
-        check(lib().bwtm_locator_create(index.h, int(max_len), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_locator_create, index.h, int(max_len))
         self.index = index
 
-    nbytes = property(lambda s: int(lib().bwtm_locator_bytes(s.h)))
+    nbytes = _scalar("bwtm_locator_bytes")
 
     def free(self):
-        if self.h:
-            lib().bwtm_locator_free(self.h)
-            self.h = None
-            self.index = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        super().free()
+        self.index = None
 
     def locate(self, positions):
         """(ids, offsets) of an array of BWT positions."""
-        if not self.h:
-            raise BwtmError("the locator has been freed")
-        positions, pp = _u64(positions)
+        self._live()
+        positions = _u64(positions)
         ids = np.zeros(positions.size, dtype=np.uint64)
         offs = np.zeros(positions.size, dtype=np.uint64)
-        check(lib().bwtm_locate_batch(self.h, pp, positions.size, ids.ctypes.data_as(p_u64), offs.ctypes.data_as(p_u64)))
+        check(lib().bwtm_locate_batch(self.h, positions, positions.size, ids, offs))
         return ids, offs
 
     def locate_ranges(self, sp, ep, max_hits=0):
         """(hit_offsets [count + 1], ids, offsets) of closed ranges [sp, ep] (sp > ep: empty): the hits of range r are
         [hit_offsets[r], hit_offsets[r + 1]) in ascending BWT position.  One sizing call, then the locating call."""
-        if not self.h:
-            raise BwtmError("the locator has been freed")
-        sp, spp = _u64(sp)
-        ep, epp = _u64(ep)
+        self._live()
+        sp, ep = _u64(sp), _u64(ep)
         assert sp.size == ep.size
-        hit_offsets = np.zeros(sp.size + 1, dtype=np.uint64)
-        check(lib().bwtm_locate_ranges(self.h, spp, epp, sp.size, int(max_hits), hit_offsets.ctypes.data_as(p_u64), None, None, 0))
-        total = int(hit_offsets[-1])
-        ids = np.zeros(total, dtype=np.uint64)
-        offs = np.zeros(total, dtype=np.uint64)
-        if total > 0:
-            check(lib().bwtm_locate_ranges(self.h, spp, epp, sp.size, int(max_hits), hit_offsets.ctypes.data_as(p_u64), ids.ctypes.data_as(p_u64),
-                                           offs.ctypes.data_as(p_u64), total))
-        return hit_offsets, ids, offs
+        return _size_then_fill(partial(lib().bwtm_locate_ranges, self.h, sp, ep, sp.size, int(max_hits)), sp.size, np.uint64, np.uint64)
 
     def locate_patterns(self, patterns, max_hits=0):
         """Every occurrence of every pattern (sequences of comp values): find, the sizing call, the locating call.  Returns
@@ -1301,17 +1203,6 @@ class Locator:
         occ_offsets, ids, offs = self.locate_ranges(sp, sp + count - np.uint64(1), max_hits)
         return hit_offsets, begin, length, sp, count, occ_offsets, ids, offs
 
-    def _overlap_calls(self, call, count, max_hits):
-        """The sizing call, then the real one: call(hit_offsets, ids, lengths, capacity) is one of the two C calls with its queries bound."""
-        hit_offsets = np.zeros(int(count) + 1, dtype=np.uint64)
-        check(call(hit_offsets.ctypes.data_as(p_u64), None, None, 0))
-        total = int(hit_offsets[-1])
-        ids = np.zeros(total, dtype=np.uint64)
-        lengths = np.zeros(total, dtype=np.uint64)
-        if total > 0:
-            check(call(hit_offsets.ctypes.data_as(p_u64), ids.ctypes.data_as(p_u64), lengths.ctypes.data_as(p_u64), total))
-        return hit_offsets, ids, lengths
-
     def overlaps(self, ids=None, first=0, count=None, min_overlap=1, max_hits=0, skip_self=False):
         """Suffix-prefix overlaps of sequences of the index (bwtm_overlap_sequences): the queries are ids (any order, repeats allowed), or
         first .. first + count - 1 (count=None: up to the last sequence).  Returns (hit_offsets [count + 1], ids, lengths): for h in
@@ -1319,20 +1210,11 @@ class Locator:
         lengths[h] >= min_overlap; longest overlap first, then targets in BWT order.  max_hits > 0 keeps the first max_hits hits of every
         query.  skip_self drops, on the host, the hit of a query with itself over its whole length and recomputes hit_offsets; it applies
         AFTER the max_hits cut, so a query can keep max_hits - 1 hits."""
-        if not self.h:
-            raise BwtmError("the locator has been freed")
-        ip = None
-        if ids is not None:
-            ids, ip = _u64(ids)
-            count = ids.size
-            queries = ids
-        else:
-            if count is None:
-                count = max(self.index.sequences - int(first), 0)
-            queries = np.arange(int(first), int(first) + int(count), dtype=np.uint64)
-        count = int(count)
-        hit_offsets, targets, lengths = self._overlap_calls(
-            lambda ho, oi, ol, cap: lib().bwtm_overlap_sequences(self.h, ip, int(first), count, int(min_overlap), int(max_hits), ho, oi, ol, cap), count, max_hits)
+        self._live()
+        ids, first, count = _ids_or_range(self.index, ids, first, count)
+        queries = ids if ids is not None else np.arange(first, first + count, dtype=np.uint64)
+        hit_offsets, targets, lengths = _size_then_fill(
+            partial(lib().bwtm_overlap_sequences, self.h, ids, first, count, int(min_overlap), int(max_hits)), count, np.uint64, np.uint64)
         if skip_self and targets.size > 0:
             per_query = np.diff(hit_offsets).astype(np.int64)
             owner = np.repeat(np.arange(count), per_query)
@@ -1349,41 +1231,23 @@ class Locator:
     def overlap_patterns(self, patterns, min_overlap, max_hits=0):
         """Suffix-prefix overlaps of patterns that need not be sequences of the index (bwtm_overlap_batch): (hit_offsets, ids, lengths) as in
         overlaps(); a pattern holds comp values 1..5 and may be longer than every sequence."""
-        if not self.h:
-            raise BwtmError("the locator has been freed")
-        lens = np.array([len(p) for p in patterns], dtype=np.uint64)
-        offsets = np.zeros(len(patterns) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum(lens)
-        text = np.concatenate([np.asarray(p, dtype=np.uint8) for p in patterns] + [np.zeros(0, dtype=np.uint8)])
-        text, tp = _u8(text)
-        return self._overlap_calls(
-            lambda ho, oi, ol, cap: lib().bwtm_overlap_batch(self.h, tp, offsets.ctypes.data_as(p_u64), len(patterns), int(min_overlap), int(max_hits), ho, oi, ol, cap),
-            len(patterns), max_hits)
+        self._live()
+        text, offsets = pack_texts(patterns)
+        return _size_then_fill(partial(lib().bwtm_overlap_batch, self.h, text, offsets, len(patterns), int(min_overlap), int(max_hits)),
+                               len(patterns), np.uint64, np.uint64)
 
 
-class RankArray:
+class RankArray(Handle):
     """Device-resident rank array (handle on bwtm_ra)."""
+    _free = "bwtm_ra_free"
 
     def __init__(self, a, b, device_buffer=None, nbytes=0):
-        out = vp()
         if device_buffer is None:
-            check(lib().bwtm_ra_create(a.h, b.h, C.byref(out)))
+            self.h = _new(lib().bwtm_ra_create, a.h, b.h)
         else:
-            check(lib().bwtm_ra_create_on(a.h, b.h, vp(device_buffer), nbytes, C.byref(out)))
-        self.h = out
+            self.h = _new(lib().bwtm_ra_create_on, a.h, b.h, vp(device_buffer), nbytes)
         self.n_out = a.bases + b.bases
         self.nb = b.bases
-
-    def free(self):
-        if self.h:
-            lib().bwtm_ra_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
     def search(self, a, b, seq_first, seq_last):
         check(lib().bwtm_search(a.h, b.h, seq_first, seq_last, self.h))
@@ -1415,24 +1279,22 @@ class RankArray:
         ones = u64(0)
         local = np.zeros(nsup, dtype=np.uint64)
         tail = np.zeros(128, dtype=np.uint64)
-        check(lib().bwtm_ra_range_counts(self.h, rec_first, rec_last, C.byref(ones), local.ctypes.data_as(p_u64), tail.ctypes.data_as(p_u64)))
+        check(lib().bwtm_ra_range_counts(self.h, rec_first, rec_last, C.byref(ones), local, tail))
         return int(ones.value), local, tail
 
     def finalize_range(self, rec_first, rec_last, ones_before, ones_total, super_boff, halo_words=None):
         """Output-range finalize, step 2 (include/bwtm.h: bwtm_ra_finalize_range)."""
-        super_boff = np.ascontiguousarray(super_boff, dtype=np.uint64)
+        super_boff, halo = _u64(super_boff), _opt_u64(halo_words)
         assert super_boff.size == (self.n_out >> 25) + 1
-        halo = None if halo_words is None else np.ascontiguousarray(halo_words, dtype=np.uint64)
         assert halo is None or halo.size == 128
-        check(lib().bwtm_ra_finalize_range(self.h, rec_first, rec_last, ones_before, ones_total, super_boff.ctypes.data_as(p_u64),
-                                           None if halo is None else halo.ctypes.data_as(p_u64)))
+        check(lib().bwtm_ra_finalize_range(self.h, rec_first, rec_last, ones_before, ones_total, super_boff, halo))
         return self
 
-    values = property(lambda s: int(lib().bwtm_ra_values(s.h)))
+    values = _scalar("bwtm_ra_values")
 
     def download(self):
         out = np.zeros(self.nb, dtype=np.uint64)
-        check(lib().bwtm_ra_download(self.h, out.ctypes.data_as(p_u64), out.size))
+        check(lib().bwtm_ra_download(self.h, out, out.size))
         return out
 
     def runs(self):
@@ -1441,35 +1303,23 @@ class RankArray:
         check(lib().bwtm_ra_download_runs(self.h, None, None, 0, C.byref(n)))
         ranks = np.zeros(n.value, dtype=np.uint64)
         counts = np.zeros(n.value, dtype=np.uint64)
-        check(lib().bwtm_ra_download_runs(self.h, ranks.ctypes.data_as(p_u64), counts.ctypes.data_as(p_u64), n.value, C.byref(n)))
+        check(lib().bwtm_ra_download_runs(self.h, ranks, counts, n.value, C.byref(n)))
         return ranks, counts
 
     def bits(self):
         words = (self.n_out + 63) // 64
         out = np.zeros(words, dtype=np.uint64)
-        check(lib().bwtm_ra_download_bits(self.h, out.ctypes.data_as(p_u64), out.size))
+        check(lib().bwtm_ra_download_bits(self.h, out, out.size))
         return out
 
 
-class Slice:
+class Slice(Handle):
     """One GPU's share of a merged index: the output records [rec_first, rec_last) (handle on bwtm_slice)."""
+    _free = "bwtm_slice_free"
 
     def __init__(self, a, b, ra, rec_first, rec_last):
-        out = vp()
-        check(lib().bwtm_interleave_range(a.h, b.h, ra.h, rec_first, rec_last, C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_interleave_range, a.h, b.h, ra.h, rec_first, rec_last)
         self.total_nbytes = 0
-
-    def free(self):
-        if self.h:
-            lib().bwtm_slice_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
     def lasthead(self):
         v = u64(0)
@@ -1478,17 +1328,17 @@ class Slice:
 
     def size_table(self, heads_before):
         t = np.zeros(64, dtype=np.uint64)
-        check(lib().bwtm_slice_size_table(self.h, int(heads_before), t.ctypes.data_as(p_u64)))
+        check(lib().bwtm_slice_size_table(self.h, int(heads_before), t))
         return t
 
     def encode(self, byte_offset):
         check(lib().bwtm_slice_encode(self.h, int(byte_offset)))
         return self
 
-    byte_first = property(lambda s: int(lib().bwtm_slice_byte_first(s.h)))
-    nbytes = property(lambda s: int(lib().bwtm_slice_bytes(s.h)))
-    block_first = property(lambda s: int(lib().bwtm_slice_block_first(s.h)))
-    blocks = property(lambda s: int(lib().bwtm_slice_blocks(s.h)))
+    byte_first = _scalar("bwtm_slice_byte_first")
+    nbytes = _scalar("bwtm_slice_bytes")
+    block_first = _scalar("bwtm_slice_block_first")
+    blocks = _scalar("bwtm_slice_blocks")
 
     def first_block_start(self):
         """Sequence position at which the slice's first block starts; None if it has no block."""
@@ -1498,24 +1348,24 @@ class Slice:
 
     def data(self):
         out = np.zeros(self.nbytes, dtype=np.uint8)
-        check(lib().bwtm_slice_download_data(self.h, out.ctypes.data_as(p_u8), out.size))
+        check(lib().bwtm_slice_download_data(self.h, out, out.size))
         return out
 
     def data_into(self, out):
         """The slice's bytes into a caller-provided uint8 array (e.g. page-locked: HostBuffer.array)."""
-        check(lib().bwtm_slice_download_data(self.h, out.ctypes.data_as(p_u8), out.size))
+        check(lib().bwtm_slice_download_data(self.h, out, out.size))
         return out[: self.nbytes]
 
     def samples(self, next_block_start):
         nb = self.blocks
         be = np.zeros(nb, dtype=np.uint64)
         cum = np.zeros((SIGMA, nb), dtype=np.uint64)
-        check(lib().bwtm_slice_download_samples(self.h, int(next_block_start), be.ctypes.data_as(p_u64), cum.ctypes.data_as(p_u64)))
+        check(lib().bwtm_slice_download_samples(self.h, int(next_block_start), be, cum))
         return be, cum
 
     def extract(self, first, count):
         out = np.zeros(count, dtype=np.uint8)
-        check(lib().bwtm_slice_extract(self.h, first, count, out.ctypes.data_as(p_u8)))
+        check(lib().bwtm_slice_extract(self.h, first, count, out))
         return out
 
 
@@ -1523,9 +1373,7 @@ class Group:
     """The parts of a merge over partitioned records (bwtm_group): `name` = a POSIX shared-memory name unique to the group (None for one part)."""
 
     def __init__(self, name, part, parts):
-        out = vp()
-        check(lib().bwtm_group_create(name.encode() if name else None, int(part), int(parts), C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_group_create, name.encode() if name else None, int(part), int(parts))
         self.part, self.parts = int(part), int(parts)
 
     def free(self):
@@ -1540,7 +1388,7 @@ class Group:
         """mine: a numpy array; returns [parts, ...] of the same dtype."""
         mine = np.ascontiguousarray(mine)
         out = np.zeros((self.parts,) + mine.shape, dtype=mine.dtype)
-        check(lib().bwtm_group_allgather(self.h, mine.ctypes.data_as(vp), mine.nbytes, out.ctypes.data_as(vp)))
+        check(lib().bwtm_group_allgather(self.h, mine.ctypes.data, mine.nbytes, out.ctypes.data))
         return out
 
     def abort(self):
@@ -1566,7 +1414,7 @@ def host_index(data, cum, sequences, bases):
 def partition_cuts_host(a, b, parts, kmer=0):
     """(cut_a, cut_b): parts + 1 ranks each (bwtm_partition_cuts_host); a, b = host_index() objects."""
     ca = np.zeros(parts + 1, dtype=np.uint64); cb = np.zeros(parts + 1, dtype=np.uint64)
-    check(lib().bwtm_partition_cuts_host(C.byref(a), C.byref(b), int(parts), int(kmer), ca.ctypes.data_as(p_u64), cb.ctypes.data_as(p_u64)))
+    check(lib().bwtm_partition_cuts_host(C.byref(a), C.byref(b), int(parts), int(kmer), ca, cb))
     return [int(v) for v in ca], [int(v) for v in cb]
 
 
@@ -1578,8 +1426,9 @@ def window_blocks(x, pos_first, pos_last):
     return int(b0.value), int(b1.value), int(fp.value), before
 
 
-class Part:
+class Part(Handle):
     """One part of a merge over partitioned records (bwtm_part): created in the calling thread's context."""
+    _free = "bwtm_part_free"
 
     def __init__(self, group, a, b, cut_a, cut_b):
         """a, b: host_index() objects (or anything with bases / sequences / C)."""
@@ -1589,21 +1438,8 @@ class Part:
             for c in range(SIGMA + 1):
                 h.C[c] = int(x.C[c])
         ca = (u64 * len(cut_a))(*[int(v) for v in cut_a]); cb = (u64 * len(cut_b))(*[int(v) for v in cut_b])
-        out = vp()
-        check(lib().bwtm_part_create(group.h, C.byref(ha), C.byref(hb), ca, cb, C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_part_create, group.h, C.byref(ha), C.byref(hb), ca, cb)
         self.group = group
-
-    def free(self):
-        if self.h:
-            lib().bwtm_part_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
     def window(self, which):
         lo, hi = u64(0), u64(0)
@@ -1661,7 +1497,7 @@ def fold_offsets(tables):
     """tables: [parts, 64] uint64 -> offsets [parts + 1] (byte offset of every slice, then the size of the stream)."""
     tables = np.ascontiguousarray(tables, dtype=np.uint64)
     out = np.zeros(tables.shape[0] + 1, dtype=np.uint64)
-    check(lib().bwtm_fold_offsets(tables.ctypes.data_as(p_u64), tables.shape[0], out.ctypes.data_as(p_u64)))
+    check(lib().bwtm_fold_offsets(tables, tables.shape[0], out))
     return out
 
 
@@ -1670,34 +1506,27 @@ def ra_buffer_bytes(a, b):
 
 
 def interleave(a, b, ra):
-    out = vp()
-    check(lib().bwtm_interleave(a.h, b.h, ra.h, C.byref(out)))
-    return Index(out)
+    return Index(_new(lib().bwtm_interleave, a.h, b.h, ra.h))
 
 
 def merge(a, b):
     """FMI::FMI(a, b): search + finalize + interleave + encode + samples on the device."""
-    out = vp()
-    check(lib().bwtm_merge(a.h, b.h, C.byref(out)))
-    return Index(out)
+    return Index(_new(lib().bwtm_merge, a.h, b.h))
 
 
 def merge_consume(a, b):
     """The same with the reference's ownership: a and b are destroyed, their memory released progressively."""
-    out = vp()
     ha, hb = a.h, b.h
     a.h = None; b.h = None
-    check(lib().bwtm_merge_consume(ha, hb, C.byref(out)))
-    return Index(out)
+    return Index(_new(lib().bwtm_merge_consume, ha, hb))
 
 
-class Builder:
+class Builder(Handle):
     """Reads -> index on the GPU (bwtm_builder_*): leaves by suffix sort, grown by the merger itself."""
+    _free = "bwtm_builder_free"
 
     def __init__(self, leaf_reads=0):
-        out = vp()
-        check(lib().bwtm_builder_create(leaf_reads, C.byref(out)))
-        self.h = out
+        self.h = _new(lib().bwtm_builder_create, leaf_reads)
 
     def add(self, reads, lengths=None):
         """reads: [n, width] uint8 numpy array of comp values 1..5 (host); lengths: optional uint32 [n]."""
@@ -1715,25 +1544,11 @@ class Builder:
         check(lib().bwtm_builder_add(self.h, vp(ptr), nreads, width, width if stride is None else stride,
                                      vp(lengths_ptr) if lengths_ptr else None, 1))
 
-    reads = property(lambda s: int(lib().bwtm_builder_reads(s.h)))
+    reads = _scalar("bwtm_builder_reads")
 
     def finish(self):
-        out = vp()
-        h = self.h
-        self.h = None
-        check(lib().bwtm_builder_finish(h, C.byref(out)))
-        return Index(out)
-
-    def free(self):
-        if self.h:
-            lib().bwtm_builder_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        h, self.h = self.h, None                           # given up before the call
+        return Index(_new(lib().bwtm_builder_finish, h))
 
 
 class PoolInfo(C.Structure):
@@ -1747,28 +1562,26 @@ def pool_stats():
     return {k: int(getattr(info, k)) for k, _ in PoolInfo._fields_}
 
 
+FIND_STATS = ("expanded", "frontier_peak", "batch_hits", "levels")
+MEM_STATS = ("steps", "tasks", "mems", "batches")
+
+
 def find_approx_stats():
     """What the calling thread's last Index.find_approx call did (bwtm_find_approx_stats; of its second, filling call when there were hits):
     nodes expanded, the largest frontier of a batch, the most hits of a batch before max_hits, levels run."""
-    stats = np.zeros(4, dtype=np.uint64)
-    check(lib().bwtm_find_approx_stats(stats.ctypes.data_as(p_u64)))
-    return dict(expanded=int(stats[0]), frontier_peak=int(stats[1]), batch_hits=int(stats[2]), levels=int(stats[3]))
+    return _stats(lib().bwtm_find_approx_stats, FIND_STATS)
 
 
 def find_edit_stats():
     """What the calling thread's last Index.find_edit call did (bwtm_find_edit_stats; of its second, filling call when there were hits):
     nodes expanded, the largest frontier of a batch, the most hits of a batch before max_hits, levels run."""
-    stats = np.zeros(4, dtype=np.uint64)
-    check(lib().bwtm_find_edit_stats(stats.ctypes.data_as(p_u64)))
-    return dict(expanded=int(stats[0]), frontier_peak=int(stats[1]), batch_hits=int(stats[2]), levels=int(stats[3]))
+    return _stats(lib().bwtm_find_edit_stats, FIND_STATS)
 
 
 def mem_stats():
     """What the calling thread's last Index.matching_stats or Index.mems call did (bwtm_mem_stats; of its second, filling call when there
     were MEMs): LF steps taken, tasks run, MEMs before min_length, batches."""
-    stats = np.zeros(4, dtype=np.uint64)
-    check(lib().bwtm_mem_stats(stats.ctypes.data_as(p_u64)))
-    return dict(steps=int(stats[0]), tasks=int(stats[1]), mems=int(stats[2]), batches=int(stats[3]))
+    return _stats(lib().bwtm_mem_stats, MEM_STATS)
 
 
 def pool_poison_stats():

@@ -14,7 +14,7 @@ import ctypes as C
 import os
 
 from . import capi
-from .capi import BwtmError, check, lib, u64, vp
+from .capi import BwtmError, Handle, _new, a_u64, check, lib, u64, vp
 from .dist import shard_range
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,7 +28,7 @@ EXPERIMENTAL_SYMBOLS = [
     ("bwtm_fslice_gather", C.c_int, [vp, vp, C.c_int, u64, u64]),
     ("bwtm_fslice_advance", C.c_int, [vp]),
     ("bwtm_fslice_finish", C.c_int, [vp]),
-    ("bwtm_x_device_scan", C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u64, u64, C.c_int]),
+    ("bwtm_x_device_scan", C.c_int, [a_u64, a_u64, u64, u64, C.c_int]),
     ("bwtm_x_index_window", C.c_int, [vp, u64, u64, C.POINTER(vp)]),
     ("bwtm_x_index_record_bytes", u64, [vp]),
     ("bwtm_x_ra_create_range", C.c_int, [vp, vp, u64, u64, C.POINTER(vp)]),
@@ -87,25 +87,13 @@ class FSliceNodesView(C.Structure):
     _fields_ = [("sp", vp), ("r", vp), ("count", vp), ("class_first", u64 * 6), ("below", (u64 * (MAX_PARTS + 1)) * 5)]
 
 
-class FSlice:
+class FSlice(Handle):
     """One GPU's state of the sliced frontier search (bwtm_fslice; include/bwtm_experimental.h)."""
+    _free = "bwtm_fslice_free"
 
     def __init__(self, a, b, ra, capacity, parts):
         _bind()
-        out = vp()
-        check(lib().bwtm_fslice_create(a.h, b.h, ra.h, capacity, parts, C.byref(out)))
-        self.h = out
-
-    def free(self):
-        if self.h:
-            lib().bwtm_fslice_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        self.h = _new(lib().bwtm_fslice_create, a.h, b.h, ra.h, capacity, parts)
 
     def seed(self, seq_first, count):
         check(lib().bwtm_fslice_seed(self.h, seq_first, count))
@@ -172,7 +160,7 @@ def device_scan(values, narrays=1, op=0):
     _bind()
     v = np.ascontiguousarray(values, dtype=np.uint64)
     out = np.empty_like(v)
-    check(lib().bwtm_x_device_scan(v.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_uint64)), v.size // narrays, narrays, op))
+    check(lib().bwtm_x_device_scan(v, out, v.size // narrays, narrays, op))
     return out
 
 
@@ -222,9 +210,7 @@ def search_sliced(pkg, indexes, ras, sequences, enter=None):
 def index_window(index, pos_first, pos_last):
     """The records of the positions [pos_first, pos_last] of `index` as a handle of their own (bwtm_x_index_window): only for FSlice / RankArray."""
     _bind()
-    out = vp()
-    check(lib().bwtm_x_index_window(index.h, int(pos_first), int(pos_last), C.byref(out)))
-    return capi.Index(out)
+    return capi.Index(_new(lib().bwtm_x_index_window, index.h, int(pos_first), int(pos_last)))
 
 
 def index_record_bytes(index):
@@ -370,18 +356,14 @@ def index_upload_window(data, cum, bases, sequences, pos_first, pos_last, starts
     before = (u64 * 6)(*[int(cum[c][b0]) for c in range(6)])
     totals = [int(cum[c][-1]) for c in range(6)]
     Cs = (u64 * 7)(*[sum(totals[:c]) for c in range(7)])
-    out = vp()
-    check(lib().bwtm_x_index_upload_window(share.ctypes.data_as(C.c_void_p), share.size, int(starts[b0]), before, int(bases), int(sequences), Cs, C.byref(out)))
-    return capi.Index(out)
+    return capi.Index(_new(lib().bwtm_x_index_upload_window, share.ctypes.data, share.size, int(starts[b0]), before, int(bases), int(sequences), Cs))
 
 
 def rank_array_range(a, b, pos_first, pos_last):
     """The rank array of one part: the bits of the output positions [pos_first, pos_last) and a tile on either side (bwtm_x_ra_create_range)."""
     _bind()
-    out = vp()
-    check(lib().bwtm_x_ra_create_range(a.h, b.h, int(pos_first), int(pos_last), C.byref(out)))
     ra = capi.RankArray.__new__(capi.RankArray)
-    ra.h = out; ra.n_out = a.bases + b.bases; ra.nb = b.bases
+    ra.h = _new(lib().bwtm_x_ra_create_range, a.h, b.h, int(pos_first), int(pos_last)); ra.n_out = a.bases + b.bases; ra.nb = b.bases
     return ra
 
 
